@@ -9,9 +9,9 @@ One "step" = one pass of the hot path over one batch (BASELINE.json configs):
       device-resident, per GPU (weak scaling: N GPUs checksum N such batches,
       so the driver's 1/2/4/8-GPU lines compare like with like)
   c4 (configs[3]): 32,768 x 1 MiB per GPU = the 256 Ki x 1 MiB batch sharded
-      over 8 GPUs (`--config c4 --gpus 8`); at every --gpus N the C2 line
-      also carries a `config_c4` sub-record: the same ranks time their C4
-      shard right after the C2 leg (so the driver's 1/2/4/8-GPU sweep also
+      over 8 GPUs (`--config c4 --gpus 8`); with --full, at every --gpus N
+      the C2 line also carries a `config_c4` sub-record: the same ranks time
+      their C4 shard right after the C2 leg (so a 1/2/4/8-GPU sweep also
       measures configs[3], weak-scaling, as SURVEY §8(d) asks; `value` stays
       C2's)
   c3: 1,048,576 x 4 KiB        c5: 65,536 messages x 8 non-contiguous 8 KiB
@@ -23,6 +23,15 @@ One "step" = one pass of the hot path over one batch (BASELINE.json configs):
   --h2d / --rpc-batch / --rpc-latency / --file-records: host-memory rates
       for DESIGN.md, never `value`; --extend: one long device buffer (the
       reference's perf shape) and the routed drop-in's costs, also DESIGN.md.
+
+A plain run sets up, warms up, times exactly --steps steps, spot-checks the
+last step's results, and prints the line. --full adds the side legs, each
+after the timed steps and outside `value`: the one-wavefront-per-buffer
+(G=64) line, the C4 leg, the live rocprofv3 FETCH_SIZE pass (without it
+`roofline.traffic` is read from the committed profiles/pmc_<config>.json)
+and the CPU baselines. --dump-outputs DIR writes what the last timed step
+computed (the CRC arrays a caller receives) as DIR/<name>.npy, float64;
+the inputs are seeded, so two builds can be compared output for output.
 
 Multi-GPU: one process per GPU. The driver launches
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`;
@@ -111,7 +120,15 @@ def parse(argv=None):
     ap.add_argument("--device", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--traffic-json", default=None,
                     help="PMC summary (profiles/*.json) giving HBM bytes per launch (fallback when no live pass)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs after the timed steps: the G=64 shape line, the C4 shard leg, the "
+                         "live rocprofv3 FETCH_SIZE pass and the CPU baselines (each still has its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: set up, warm up, time the steps, report
+        args.no_shape64 = args.no_c4_leg = args.no_live_pmc = args.no_cpu_baseline = True
+    return args
 
 
 # ------------------------------------------------------------------ launcher
@@ -200,6 +217,14 @@ def aggregate_gibps(bytes_per_step_per_rank, steps, world, elapsed):
     return bytes_per_step_per_rank * steps * world / elapsed / GIB
 
 
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: every array as path/<name>.npy (rank r of an N>1 job
+    writes <name>_rank<r>.npy: each rank has its own shard's results)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def launch_summary(ms):
     a = np.asarray(ms, dtype=np.float64)
     return {"first5": [round(float(x), 4) for x in a[:5]], "mean": round(float(a.mean()), 4),
@@ -246,6 +271,19 @@ class Workload:
         else:
             ck.batch_msg_n(self.iov, self.start, c["count"], c["count"] * c["nseg"],
                            self.seg_out if c.get("seg_out") else None, self.out, stream=self.stream)
+
+    def outputs(self):
+        """What a caller of step() receives, as float64 arrays (every value a
+        whole number below 2^32, so exact): the per-buffer / per-message CRCs,
+        a CRC-64 as its (high, low) 32-bit halves, and C5's per-segment CRCs."""
+        c = self.cfg
+        if c["kind"] == "strided64":
+            v = self.out.cpu().numpy().view(np.uint64)
+            return {"crc64ecma_hi_lo": np.stack([v >> np.uint64(32), v & np.uint64(0xFFFFFFFF)], 1).astype(np.float64)}
+        res = {"crc32c": self.out.cpu().numpy().view(np.uint32).astype(np.float64)}
+        if c["kind"] == "msg" and c.get("seg_out"):
+            res["crc32c_segments"] = self.seg_out.cpu().numpy().view(np.uint32).astype(np.float64)
+        return res
 
     def self_check(self):
         """Spot-check the LAST timed step's results against the product's own
@@ -892,6 +930,8 @@ def run_cpu_rehearsal(args, rank, world, dist):
         return lambda: dt
 
     elapsed, _, local_el, local_ms = timed_region(step, args.steps, args.warmup, lambda: None, dist, on_step)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"crc32c": np.asarray(out, dtype=np.float64)}, rank, world)
     ranks = gather_ranks(dist, {"rank": rank, "wall_s": round(local_el, 6), "first_crc": int(out[0]),
                                 "launch_ms": launch_summary(local_ms)})
     c4 = None
@@ -1000,6 +1040,8 @@ def main(argv=None):
     elapsed, kernel_ms, local_el, local_ms = timed_region(wl.step, args.steps, args.warmup, torch.cuda.synchronize,
                                                           dist, on_step)
     ok = wl.self_check()  # the last timed step's results, checked after the timed region
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl.outputs(), rank, world)
     bytes_step = wl.bytes_per_step
     value = aggregate_gibps(wl.bytes_per_step, args.steps, world, elapsed)
     per_launch_gbps = wl.bytes_per_step / (kernel_ms * 1e-3) / 1e9

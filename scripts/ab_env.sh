@@ -11,7 +11,7 @@ for r in $(seq 1 $rounds); do
     IFS='|' read -r envs args <<< "$arm"
     envs=$(eval echo "$envs")
     env $envs timeout -k 10 300 python -u bench.py --config $c $args ${AB_ARGS:---steps 200 --warmup 25} \
-      --no-cpu-baseline --no-live-pmc --no-shape64 > $O/ab_tmp.json 2>> $O/ab_env.err || { echo "run $arm failed"; tail -5 $O/ab_env.err; exit 1; }
+      --full --no-cpu-baseline --no-live-pmc --no-shape64 > $O/ab_tmp.json 2>> $O/ab_env.err || { echo "run $arm failed"; tail -5 $O/ab_env.err; exit 1; }
     python -c "import json,sys; d=json.loads(open('$O/ab_tmp.json').read().splitlines()[-1]); r=d['roofline']; print(json.dumps({'round': $r, 'config': '$c', 'arm': sys.argv[1], 'value': d['value'], 'frac_kernel': r['frac_kernel'], 'frac_steady': r['frac_steady_median_launch'], 'ok': d['self_check']}))" "$arm" | tee -a $O/ab_env.jsonl
   done
 done

@@ -42,12 +42,12 @@ run_one() {
       local c=$1; shift
       local pt; pt=$(echo "$c $*" | tr -c 'a-zA-Z0-9_' '_' | sed 's/__*/_/g;s/^_//;s/_$//')  # prof c2 --extend -> prof_c2_extend
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$pt -o $c -- \
-        python3 bench.py --config $c --no-cpu-baseline --no-live-pmc "$@" > $O/prof_$pt.log 2>&1 \
+        python3 bench.py --config $c --full --no-cpu-baseline --no-live-pmc "$@" > $O/prof_$pt.log 2>&1 \
         || { echo "prof $c failed"; tail -20 $O/prof_$pt.log; return 1; } ;;
     pmc)
       local c=$1
       timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_$c -o $c -- \
-        python3 bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline --no-live-pmc --no-shape64 > $O/pmc_$c.log 2>&1 \
+        python3 bench.py --config $c --steps 5 --warmup 2 --full --no-cpu-baseline --no-live-pmc --no-shape64 > $O/pmc_$c.log 2>&1 \
         || { echo "pmc $c failed"; tail -20 $O/pmc_$c.log; return 1; } ;;
     sq)
       bash scripts/pmc_kernel.sh $1 $O/sq_$1 > /dev/null || { echo "sq $1 failed"; return 1; } ;;
@@ -64,7 +64,7 @@ run_one() {
           for side in new old; do
             local envv=""; [ $side = old ] && envv="PHOTON_CRC_LIB=$lib"
             [ $side = new ] && [ -n "$AB_NEW" ] && envv="PHOTON_CRC_LIB=$AB_NEW"
-            env $envv timeout -k 10 300 python -u bench.py --config $c --no-cpu-baseline --no-live-pmc --no-shape64 $AB_ARGS \
+            env $envv timeout -k 10 300 python -u bench.py --config $c --full --no-cpu-baseline --no-live-pmc --no-shape64 $AB_ARGS \
               > $O/ab_tmp.json 2>> $O/ab.err || [ "$(wc -l < $O/ab_tmp.json)" -gt 0 ] \
               || { echo "ab $c $side failed"; tail -5 $O/ab.err; return 1; }  # (self-check false still prints its line: ablation builds)
             python -c "import json,sys; d=json.loads(open('$O/ab_tmp.json').read().splitlines()[-1]); r=d['roofline']; print(json.dumps({'round': $r, 'config': '$c', 'side': '$side', 'args': '$AB_ARGS', 'value': d['value'], 'frac_kernel': r['frac_kernel'], 'frac_steady': r['frac_steady_median_launch'], 'ok': d['self_check']}))" | tee -a $O/ab.jsonl
@@ -80,7 +80,7 @@ run_one() {
         [ $((r % 2)) -eq 0 ] && order=($(printf '%s\n' "${libs[@]}" | tac))
         for lib in "${order[@]}"; do
           local envv=""; [ $lib != new ] && envv="PHOTON_CRC_LIB=$lib"
-          env $envv timeout -k 10 300 python -u bench.py --config $c --no-cpu-baseline --no-live-pmc --no-shape64 $AB_ARGS \
+          env $envv timeout -k 10 300 python -u bench.py --config $c --full --no-cpu-baseline --no-live-pmc --no-shape64 $AB_ARGS \
             > $O/ab_tmp.json 2>> $O/ab.err || [ "$(wc -l < $O/ab_tmp.json)" -gt 0 ] \
             || { echo "abn $c $lib failed"; tail -5 $O/ab.err; return 1; }
           python -c "import json,sys; d=json.loads(open('$O/ab_tmp.json').read().splitlines()[-1]); r=d['roofline']; print(json.dumps({'round': $r, 'config': '$c', 'lib': '$lib', 'value': d['value'], 'frac_kernel': r['frac_kernel'], 'frac_steady': r['frac_steady_median_launch'], 'ok': d['self_check']}))" | tee -a $O/abn.jsonl

@@ -339,7 +339,12 @@ def test_ioalloc_binding_against_reference_headers(torch_dev):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = os.path.join(repo, "oracle", "_ref", "ioalloc_dropin")
     assert os.path.exists(exe), "oracle/_ref/ioalloc_dropin not built (make -C oracle/ref in the build container)"
-    r = subprocess.run([exe, "pinned", "200"], capture_output=True, text=True, timeout=120)
+    # The program is built where the reference is and may be run from a tree at
+    # another path (or through a link): name this tree's library for it.
+    libdir = os.path.join(repo, "photonlibos_amd", "lib")
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(
+        p for p in (libdir, os.environ.get("LD_LIBRARY_PATH")) if p))
+    r = subprocess.run([exe, "pinned", "200"], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 0, r.stderr
     got = json.loads(r.stdout)
     with open(os.path.join(repo, "tests", "golden", "ioalloc_binding.json")) as f:

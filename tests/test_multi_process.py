@@ -146,7 +146,7 @@ def test_two_rank_line_carries_c4_leg():
     the same ranks after the C2 leg; each rank checksummed ITS part of the C4
     batch (global ids r*32768..)."""
     from photonlibos_amd import datagen
-    r = _run_bench("--gpus", "2", "--cpu-rehearsal", "--steps", "2", "--warmup", "1")
+    r = _run_bench("--gpus", "2", "--cpu-rehearsal", "--full", "--steps", "2", "--warmup", "1")
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert res["config"]["workload"] == bench.CONFIGS["c2"]["workload"]
@@ -162,10 +162,10 @@ def test_two_rank_line_carries_c4_leg():
     assert c4["value"] == pytest.approx(2 * 2 * 4 * (1 << 20) / slow / (1 << 30), rel=0.05)
     # the one-GPU line carries it too (the driver's 1/2/4/8 sweep measures
     # C4 weak scaling), and --no-c4-leg drops it
-    r1 = _run_bench("--gpus", "1", "--cpu-rehearsal", "--steps", "1", "--warmup", "0")
+    r1 = _run_bench("--gpus", "1", "--cpu-rehearsal", "--full", "--steps", "1", "--warmup", "0")
     one = json.loads([ln for ln in r1.stdout.splitlines() if ln.startswith("{")][0])
     assert one["config_c4"]["buffers_total"] == 32768 and one["config"]["config"] == "c2"
-    r0 = _run_bench("--gpus", "2", "--cpu-rehearsal", "--steps", "1", "--warmup", "0", "--no-c4-leg")
+    r0 = _run_bench("--gpus", "2", "--cpu-rehearsal", "--full", "--steps", "1", "--warmup", "0", "--no-c4-leg")
     assert "config_c4" not in json.loads([ln for ln in r0.stdout.splitlines() if ln.startswith("{")][0])
 
 
@@ -180,7 +180,8 @@ def test_two_rank_line_carries_cpu_baseline_and_traffic():
     the timed legs, the other ranks idle in a barrier) and the HBM traffic of
     the config's kernel with its source and scope (rank 0's device). Before
     round 6 both were gated on world == 1."""
-    r = _run_bench("--gpus", "2", "--cpu-rehearsal", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.3")
+    r = _run_bench("--gpus", "2", "--cpu-rehearsal", "--full", "--steps", "2", "--warmup", "1",
+                   "--cpu-seconds", "0.3")
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     base = res["cpu_baseline"]
@@ -191,9 +192,28 @@ def test_two_rank_line_carries_cpu_baseline_and_traffic():
     # the committed C2 profile is what a rehearsal (no rocprofv3 child) reads
     assert roof["traffic"] == bench.load_traffic(None, "c2")
     # --no-cpu-baseline drops the leg at any N
-    r0 = _run_bench("--gpus", "2", "--cpu-rehearsal", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    r0 = _run_bench("--gpus", "2", "--cpu-rehearsal", "--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
                     "--no-c4-leg")
     assert "cpu_baseline" not in json.loads([ln for ln in r0.stdout.splitlines() if ln.startswith("{")][0])
+
+
+def test_plain_run_is_lean_and_dumps_outputs(oracle, tmp_path):
+    """A plain run (no --full) times its steps and reports: no C4 leg, no CPU
+    baseline. --dump-outputs writes the last timed step's CRCs as float64
+    .npy, the same from run to run (seeded inputs)."""
+    import numpy as np
+    from photonlibos_amd import datagen
+    assert not bench.parse([]).full and bench.parse(["--full"]).full
+    r = _run_bench("--gpus", "1", "--cpu-rehearsal", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    assert "config_c4" not in res and "cpu_baseline" not in res and "cpu_reference_c1" not in res
+    assert os.listdir(tmp_path) == ["crc32c.npy"]
+    got = np.load(tmp_path / "crc32c.npy")
+    assert got.dtype == np.float64 and got.shape == (64,)
+    want = [oracle.crc32c(datagen.stream_bytes(bench.shard_seed_base(0, 64) + i, 65536)) for i in range(64)]
+    assert got.tolist() == want
 
 
 def test_pmc_child_env_leaves_the_rendezvous(monkeypatch):
