@@ -134,6 +134,46 @@ int photon_crc32c_batch_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_m
                               uint64_t nseg, uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_seg_out,
                               uint32_t* d_out, void* stream);
 
+/* (iv) Copy + CRC-32C in one pass: the payload is landed at a destination
+ * and checksummed from the same read (the unfused pair, photon_crc_memcpy_async
+ * then a batch, reads every byte twice). Asynchronous on `stream` like the
+ * batches above: nothing is allocated or synchronised inside the call, so
+ * each can be captured into a graph; 0 or a negative errno; no CPU fallback
+ * (without a usable gfx950 device: a negative code).
+ *   - Sources are device-accessible memory: HBM, or pinned / registered host
+ *     memory, which the kernel reads over the link in place. Destinations
+ *     are device-accessible.
+ *   - A source and a destination range must not overlap, nor may two
+ *     destinations: the caller's responsibility, not checked.
+ *   - Bytes outside [dst, dst + len) are never written.
+ *   - A zero-length buffer writes nothing and returns the seed.
+ *   - Null pointers with a non-zero count give -EINVAL; count == 0 /
+ *     nmsg == 0 return 0.
+ *   - Any alignment is correct; the payload is read exactly once when source
+ *     and destination are co-aligned ((dst - src) % 16 == 0), else the
+ *     buffer is copied first and checksummed from the cache.
+ *
+ * dst buffer i = d_dst_base + i*dst_stride receives the nbytes of src buffer
+ * i = src_base + i*src_stride; d_out[i] = crc32c_extend(src_i, nbytes, seed_i). */
+int photon_crc32c_copy_batch_strided(const void* src_base, uint64_t src_stride,
+                                     void* d_dst_base, uint64_t dst_stride,
+                                     uint64_t nbytes, uint64_t count, uint32_t seed0,
+                                     const uint32_t* d_seeds, uint32_t* d_out, void* stream);
+
+/* d_dst[i] receives d_src[i].len bytes from d_src[i].base (d_src and d_dst:
+ * device-resident arrays of count entries). */
+int photon_crc32c_copy_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst,
+                                 uint64_t count, uint32_t seed0, const uint32_t* d_seeds,
+                                 uint32_t* d_out, void* stream);
+
+/* iovector_view::memcpy_to + Crc32Hasher in one pass: message m's segments
+ * are written back to back at d_dst[m]; d_out / d_seg_out exactly as
+ * photon_crc32c_batch_msg_n (d_seg_out optional). */
+int photon_crc32c_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_msg_start,
+                               uint64_t nmsg, uint64_t nseg, void* const* d_dst,
+                               uint32_t seed0, const uint32_t* d_seeds,
+                               uint32_t* d_seg_out, uint32_t* d_out, void* stream);
+
 /* d_out[i] = crc32c_combine(d_crc1[i], d_crc2[i], d_len2[i]) with the
  * reference's shortcuts (crc1 == 0 -> crc2, len2 == 0 -> crc1). */
 int photon_crc32c_combine_batch(const uint32_t* d_crc1, const uint32_t* d_crc2, const uint32_t* d_len2,

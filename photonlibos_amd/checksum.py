@@ -26,6 +26,7 @@ __all__ = [
     "crc32c_trim", "crc32c_trim_sw", "crc32c_trim_hw", "is_crc32c_hw_available",
     "device_count", "set_lanes_per_buffer", "host_batch_strided", "host_batch_strided_multi", "batch_strided_shards",
     "Shard", "batch_strided", "batch_strided_sync", "batch_iov", "batch_msg",
+    "copy_batch_strided", "copy_batch_iov", "gather_msg_n",
     "crc64ecma", "crc64ecma_extend", "crc64ecma_sw", "crc64ecma_hw", "crc64ecma_combine", "crc64ecma_series",
     "crc64ecma_combine_series", "crc64ecma_trim",
     "batch64_strided", "batch64_iov", "combine64_batch", "trim64_batch", "batch64_msg_n", "host_batch64_strided", "extend64_device", "extend_spans", "extend64_spans", "Span", "combine_batch", "fill_splitmix", "read_stream", "IOVEC_DTYPE",
@@ -326,6 +327,28 @@ def batch_msg_n(iov, msg_start, nmsg, nseg, seg_out, out, seed=0, seeds=None, st
     """batch_msg with the total segment count supplied (fully asynchronous)."""
     _check(lib().photon_crc32c_batch_msg_n(_ptr(iov), _ptr(msg_start), nmsg, nseg, seed & 0xFFFFFFFF, _ptr(seeds),
                                            _ptr(seg_out), _ptr(out), _stream(stream)))
+
+
+def copy_batch_strided(src, src_stride, dst, dst_stride, nbytes, count, out, seed=0, seeds=None, stream=None):
+    """dst + i*dst_stride receives the nbytes at src + i*src_stride, and out[i] =
+    crc32c_extend of them (seeds[i] or seed): copy + CRC in one read. Async."""
+    _check(lib().photon_crc32c_copy_batch_strided(_ptr(src), src_stride, _ptr(dst), dst_stride, nbytes, count,
+                                                  seed & 0xFFFFFFFF, _ptr(seeds), _ptr(out), _stream(stream)))
+
+
+def copy_batch_iov(src_iov, dst_ptrs, count, out, seed=0, seeds=None, stream=None):
+    """dst_ptrs[i] (a device array of pointers) receives src_iov[i].len bytes from
+    src_iov[i].base; out[i] = crc32c_extend(src_i, len_i, seed_i). Async."""
+    _check(lib().photon_crc32c_copy_batch_iov(_ptr(src_iov), _ptr(dst_ptrs), count, seed & 0xFFFFFFFF, _ptr(seeds),
+                                              _ptr(out), _stream(stream)))
+
+
+def gather_msg_n(iov, msg_start, nmsg, nseg, dst_ptrs, seg_out, out, seed=0, seeds=None, stream=None):
+    """batch_msg_n that also gathers: message m's segments are written back to
+    back at dst_ptrs[m] (iovector_view::memcpy_to + Crc32Hasher in one pass). Async."""
+    _check(lib().photon_crc32c_gather_msg_n(_ptr(iov), _ptr(msg_start), nmsg, nseg, _ptr(dst_ptrs),
+                                            seed & 0xFFFFFFFF, _ptr(seeds), _ptr(seg_out), _ptr(out),
+                                            _stream(stream)))
 
 
 def batch64_strided(base, stride, nbytes, count, out, seed=0, seeds=None, stream=None):

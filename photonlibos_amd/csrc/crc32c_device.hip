@@ -496,6 +496,48 @@ int launch_batch(const BatchArgs& a, uint64_t typical_len, hipStream_t stream, i
     return 0;
 }
 
+// The copying kernels (crc32c_batch_kernel<G, U, MSG, true>): one build per
+// lane-group size, with the default rows per step of that size
+// (photon_crc_set_generic_rows does not apply; photon_crc_set_lanes_per_buffer
+// does). msg: 0 = buffers, 1 = messages chained, 2 = messages with per-segment
+// CRCs; units = buffers or messages.
+int launch_copy(const CopyBatchArgs& a, int msg, uint64_t units, int g, hipStream_t stream) {
+    if (units == 0) return 0;
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint64_t gpw = 64 / g;
+    const uint64_t waves = (units + gpw - 1) / gpw;
+    uint64_t grid = (waves + kWaves - 1) / kWaves;
+    if (grid > (uint64_t)cus) grid = cus;
+    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
+    const LaneConsts& kc = lane_consts(g);
+    HeavyLaunch heavy(stream);
+#define LC(GG, UU)                                                                                                     \
+    do {                                                                                                               \
+        if (msg == 2)                                                                                                  \
+            hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU, 2, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc,     \
+                               pow_table());                                                                           \
+        else if (msg == 1)                                                                                             \
+            hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU, 1, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc,     \
+                               pow_table());                                                                           \
+        else                                                                                                           \
+            hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU, 0, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc,     \
+                               pow_table());                                                                           \
+    } while (0)
+    switch (g) {
+        case 64: LC(64, 4); break;
+        case 32: LC(32, 4); break;
+        case 16: LC(16, 2); break;
+        case 8: LC(8, 4); break;
+        default: LC(4, 4); break;
+    }
+#undef LC
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "crc32c_batch_kernel<copy> launch");
+    return 0;
+}
+
 LaneConsts64 make_lane_consts64(int g) {
     LaneConsts64 c;
     c.kshift = xpow64(8ull * 16ull * (uint64_t)g);
@@ -1540,6 +1582,64 @@ int photon_crc32c_batch_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_m
                               uint64_t nseg, uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_seg_out,
                               uint32_t* d_out, void* stream) {
     return pcrc::batch_msg_lanes(d_iov, d_msg_start, nmsg, nseg, seed0, d_seeds, d_seg_out, d_out, stream, 0);
+}
+
+// Copy + CRC-32C in one pass (crc32c_gpu.h; DESIGN.md "Copy + CRC").
+int photon_crc32c_copy_batch_strided(const void* src_base, uint64_t src_stride, void* d_dst_base,
+                                     uint64_t dst_stride, uint64_t nbytes, uint64_t count, uint32_t seed0,
+                                     const uint32_t* d_seeds, uint32_t* d_out, void* stream) {
+    if (!count) return 0;
+    if (!d_out || ((!src_base || !d_dst_base) && nbytes)) return fail(-EINVAL, "null source, destination or output");
+    CopyBatchArgs a{};
+    a.base = static_cast<const uint8_t*>(src_base);
+    a.stride = src_stride;
+    a.nbytes = nbytes;
+    a.count = count;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.seed0 = seed0;
+    a.dst_base = static_cast<uint8_t*>(d_dst_base);
+    a.dst_stride = dst_stride;
+    if (PCRC_SHIFT_INIT && !d_seeds && !(reinterpret_cast<uintptr_t>(src_base) & 15) && !(src_stride & 15) &&
+        nbytes >= 64) {
+        a.shift_init = 1;
+        a.init_shift = mulmod(seed0, xpow(8ull * nbytes));
+    }
+    return launch_copy(a, 0, count, batch_lanes(nbytes), static_cast<hipStream_t>(stream));
+}
+
+int photon_crc32c_copy_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t count, uint32_t seed0,
+                                 const uint32_t* d_seeds, uint32_t* d_out, void* stream) {
+    if (!count) return 0;
+    if (!d_src || !d_dst || !d_out) return fail(-EINVAL, "null descriptor array, destination array or output");
+    CopyBatchArgs a{};
+    a.iov = d_src;
+    a.count = count;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.seed0 = seed0;
+    a.dst = d_dst;
+    return launch_copy(a, 0, count, batch_lanes(65536), static_cast<hipStream_t>(stream));
+}
+
+int photon_crc32c_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_msg_start, uint64_t nmsg,
+                               uint64_t nseg, void* const* d_dst, uint32_t seed0, const uint32_t* d_seeds,
+                               uint32_t* d_seg_out, uint32_t* d_out, void* stream) {
+    if (!nmsg) return 0;
+    if (!d_msg_start || !d_dst || !d_out || (!d_iov && nseg)) return fail(-EINVAL, "null argument");
+    // Always the one-kernel form (a lane group walks its message's segments
+    // and keeps the running destination); lane groups as batch_msg_n takes.
+    CopyBatchArgs a{};
+    a.iov = d_iov;
+    a.count = nseg;
+    a.out = d_seg_out;
+    a.msg_start = d_msg_start;
+    a.nmsg = nmsg;
+    a.msg_out = d_out;
+    a.seeds = d_seeds;
+    a.seed0 = seed0;
+    a.dst = d_dst;
+    return launch_copy(a, d_seg_out ? 2 : 1, nmsg, choose_lanes(8192), static_cast<hipStream_t>(stream));
 }
 
 int photon_crc64ecma_batch_strided(const void* d_base, uint64_t stride, uint64_t nbytes, uint64_t count,

@@ -138,6 +138,15 @@ __device__ __forceinline__ uint32_t lds_word(const uint32_t* lds, uint32_t byte_
 // Per-lane lookup constants: the data word is rotated right by 8q bits
 // (byte i of the rotated word = byte (i+q)%4), and off[i] = ((i+q)%4)*32 +
 // r*4 locates slice (i+q)%4, replica r inside a table row.
+// The copying kernels (crc32c_batch_kernel<G, U, MSG, true>): where unit i's
+// bytes go. Buffer batches: dst[i], or dst_base + i*dst_stride when dst is
+// null; messages: dst[m], the message's segments back to back.
+struct CopyBatchArgs : BatchArgs {
+    uint8_t* dst_base;
+    uint64_t dst_stride;
+    void* const* dst;
+};
+
 struct LaneAddr {
     uint32_t rot;      // 8*q
     uint32_t off[4];
@@ -290,6 +299,31 @@ __device__ __forceinline__ uint4 load16(const uint8_t* p) {
 }
 
 __device__ __forceinline__ uint8_t load8(const uint8_t* p) { return *(g_u8*)p; }
+
+// The copying kernels' stores (DESIGN.md "Copy + CRC"): plain global stores.
+typedef __attribute__((address_space(1))) u32x4 g_u32x4_w;
+typedef __attribute__((address_space(1))) uint32_t g_u32_w;
+typedef __attribute__((address_space(1))) uint8_t g_u8_w;
+typedef u32x4 __attribute__((aligned(1))) u32x4_u;
+typedef __attribute__((address_space(1))) const u32x4_u g_u32x4_u;
+__device__ __forceinline__ void store16(uint8_t* p, uint4 v) { *(g_u32x4_w*)p = u32x4{v.x, v.y, v.z, v.w}; }
+__device__ __forceinline__ void store4(uint8_t* p, uint32_t v) { *(g_u32_w*)p = v; }
+__device__ __forceinline__ void store1(uint8_t* p, uint8_t v) { *(g_u8_w*)p = v; }
+// 16 bytes from any address (the copy loop of buffers whose destination is
+// not co-aligned with the source).
+__device__ __forceinline__ uint4 load16_any(const uint8_t* p) {
+    const u32x4 v = *(g_u32x4_u*)p;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// Where a copying kernel writes the blocks it reads: the byte at source
+// address a goes to a + dd. st: this buffer's blocks are stored from the CRC
+// path's registers (source and destination co-aligned, dd % 16 == 0, or a tiny
+// buffer); else group_copy has moved the bytes and the CRC path stores nothing.
+struct CopyTo {
+    ptrdiff_t dd = 0;
+    bool st = false;
+};
 
 // Basis of a multiplication by a fixed constant (image of every register bit),
 // computed at compile time: a table entry (b << 8t) * K is then the XOR of 8
@@ -662,10 +696,48 @@ __device__ __forceinline__ void buf_preload(const BufGeo& g, uint32_t gl, BufPre
 }
 
 // The lane's lagged column partial Q over every row (the preloaded ones first).
-template <int G, int U, bool LEAD = false>
+// Block 0 of a buffer that starts s0 > 0 bytes into it: bytes s0..15 of the
+// raw block with 4-byte stores where a word is all data and 1-byte stores in
+// the word the data starts in -- never a byte before the buffer's first.
+__device__ __forceinline__ void store_head(uint8_t* d, uint4 w, int s0) {
+    const uint32_t v[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int k = s0 - 4 * i;  // the data starts k bytes into word i
+        if (k <= 0) {
+            store4(d + 4 * i, v[i]);
+        } else {
+#pragma unroll
+            for (int b = 1; b < 4; ++b)
+                if (b >= k) store1(d + 4 * i + b, (uint8_t)(v[i] >> (8 * b)));
+        }
+    }
+}
+
+// COPY (the copying kernels, DESIGN.md "Copy + CRC"): every 16-byte block a
+// lane takes into the CRC is also stored at the same offset from the
+// destination's aligned start, under the condition that lets it into the CRC
+// (the preload's discarded re-reads of the aligned start store nothing).
+template <int G, int U, bool LEAD = false, bool COPY = false>
 __device__ __forceinline__ uint32_t buf_body(const uint32_t* lds, const BufGeo& g, const BufPre<U, LEAD>& pre,
-                                             uint32_t seed, uint32_t gl, const LaneAddr& la, bool head = true) {
+                                             uint32_t seed, uint32_t gl, const LaneAddr& la, bool head = true,
+                                             CopyTo ct = {}) {
+    static_assert(!COPY || PCRC_BODY == 0, "the copying kernels are built with the default row loop only");
     if (g.tiny) return 0;
+    // COPY: row `r` of this lane's column, from the registers that hold it
+    auto put = [&](uint64_t r, const uint4& v) {
+        if constexpr (COPY) {
+            if (ct.st) store16(const_cast<uint8_t*>(g.lp) + r * (16 * G) + ct.dd, v);
+        }
+    };
+    if constexpr (COPY) {
+        // Row 0 from the RAW block (w below is head-masked and seed-mixed).
+        if (ct.st && gl < g.nb) {
+            uint8_t* d = const_cast<uint8_t*>(g.lp) + ct.dd;
+            if (gl == 0 && g.s0) store_head(d, pre.w0, g.s0);
+            else store16(d, pre.w0);
+        }
+    }
     // Row 0 holds the head: masked leading bytes + seed (branch-free; lanes
     // without a block in row 0 feed a zero block, whose lagged CRC is 0).
     // head == false (uniform): an aligned buffer whose seed enters later.
@@ -685,7 +757,10 @@ __device__ __forceinline__ uint32_t buf_body(const uint32_t* lds, const BufGeo& 
         const uint32_t lead = g.full >= 1 ? (uint32_t)((g.full - 1) % U) : 0u;
 #pragma unroll
         for (int u = 0; u < U - 1; ++u)
-            if ((uint32_t)u < lead) pc = sstep(lds, pc, la, lag16(lds, pre.wl[u], la));
+            if ((uint32_t)u < lead) {
+                put(1 + u, pre.wl[u]);
+                pc = sstep(lds, pc, la, lag16(lds, pre.wl[u], la));
+            }
         row += lead;
     }
     const uint8_t* lp = g.lp;
@@ -733,11 +808,14 @@ __device__ __forceinline__ uint32_t buf_body(const uint32_t* lds, const BufGeo& 
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 c[u] = lag16(lds, cur[u], la);
+                put(row + u, cur[u]);  // before the reload takes the register
                 cur[u] = load16(lp + (row + U + u) * (16 * G));
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) pc = sstep(lds, pc, la, c[u]);
         }
+#pragma unroll
+        for (int u = 0; u < U; ++u) put(row + u, cur[u]);
         pc = lag_column_step<U>(lds, pc, cur, la);
         row += U;
         } else {
@@ -749,10 +827,14 @@ __device__ __forceinline__ uint32_t buf_body(const uint32_t* lds, const BufGeo& 
             uint4 nxt[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) nxt[u] = load16(lp + (row + U + u) * (16 * G));
+#pragma unroll
+            for (int u = 0; u < U; ++u) put(row + u, cur[u]);
             pc = lag_column_step<U>(lds, pc, cur, la);
 #pragma unroll
             for (int u = 0; u < U; ++u) cur[u] = nxt[u];
         }
+#pragma unroll
+        for (int u = 0; u < U; ++u) put(row + u, cur[u]);
         pc = lag_column_step<U>(lds, pc, cur, la);
         row += U;
         }
@@ -760,11 +842,22 @@ __device__ __forceinline__ uint32_t buf_body(const uint32_t* lds, const BufGeo& 
     }
     const bool part = g.full >= 1 && g.full < g.rows && g.full * G + gl < g.nb;
     if constexpr (LEAD) {
-        if (part) pc = sstep(lds, pc, la, lag16(lds, pre.wp, la));
+        if (part) {
+            put(g.full, pre.wp);
+            pc = sstep(lds, pc, la, lag16(lds, pre.wp, la));
+        }
     } else {
-        for (; row < g.full; ++row) pc = sstep(lds, pc, la, lag16(lds, load16(lp + row * (16 * G)), la));
+        for (; row < g.full; ++row) {
+            const uint4 v = load16(lp + row * (16 * G));
+            put(row, v);
+            pc = sstep(lds, pc, la, lag16(lds, v, la));
+        }
         // Partial last row.
-        if (part) pc = sstep(lds, pc, la, lag16(lds, load16(lp + g.full * (16 * G)), la));
+        if (part) {
+            const uint4 v = load16(lp + g.full * (16 * G));
+            put(g.full, v);
+            pc = sstep(lds, pc, la, lag16(lds, v, la));
+        }
     }
     return pc;
 }
@@ -808,32 +901,72 @@ __device__ __forceinline__ uint32_t finish_group(const uint32_t* lds, uint32_t p
 // the ragged tail (< 16 bytes); tiny buffers byte-serially. Valid on EVERY
 // lane of the group (the byte-serial parts run on all of them: same bytes,
 // same loads), so message chains need no broadcast from the first lane.
-template <int G>
+// COPY: every lane loads the tiny buffer's / the tail's bytes as before, and
+// byte k is stored by lane k mod G alone.
+template <int G, bool COPY = false>
 __device__ __forceinline__ uint32_t buf_finish(const uint32_t* lds, const BufGeo& g, uint32_t pc,
                                                const uint8_t* p, uint64_t n, uint32_t seed, uint32_t gl,
-                                               const LaneAddr& la) {
+                                               const LaneAddr& la, CopyTo ct = {}) {
     uint32_t crc;
     if (g.tiny) {
         crc = seed;
-        for (uint64_t k = 0; k < n; ++k) crc = bytestep(lds, crc, load8(p + k), la);
+        for (uint64_t k = 0; k < n; ++k) {
+            const uint8_t b = load8(p + k);
+            if constexpr (COPY) {
+                if (ct.st && ((uint32_t)k & (G - 1)) == gl) store1(const_cast<uint8_t*>(p) + k + ct.dd, b);
+            }
+            crc = bytestep(lds, crc, b, la);
+        }
         return crc;
     }
     const uint32_t d = (g.rlast + G - 1 - gl) & (G - 1);
     crc = finish_group<G>(lds, pc, d, la);
-    for (const uint8_t* q = g.eb; q < g.e; ++q) crc = bytestep(lds, crc, load8(q), la);
+    for (const uint8_t* q = g.eb; q < g.e; ++q) {
+        const uint8_t b = load8(q);
+        if constexpr (COPY) {
+            if (ct.st && ((uint32_t)(q - g.eb) & (G - 1)) == gl) store1(const_cast<uint8_t*>(q) + ct.dd, b);
+        }
+        crc = bytestep(lds, crc, b, la);
+    }
     return crc;
+}
+
+// The copy of a buffer whose destination is NOT co-aligned with its source
+// (n >= 64), by the group's G lanes before the CRC path reads the source
+// again (then from L2): the destination's whole 16-byte blocks with one
+// 16-byte store each from an unaligned 16-byte load, its head and tail (< 16
+// bytes each) byte by byte; every byte is written by exactly one lane.
+template <int G>
+__device__ __forceinline__ void group_copy(const uint8_t* p, uint8_t* d, uint64_t n, uint32_t gl) {
+    const uint64_t hd = (0 - reinterpret_cast<uintptr_t>(d)) & 15u;
+    for (uint64_t k = gl; k < hd; k += G) store1(d + k, load8(p + k));
+    const uint64_t nblk = (n - hd) >> 4;
+    for (uint64_t b = gl; b < nblk; b += G) store16(d + hd + 16 * b, load16_any(p + hd + 16 * b));
+    for (uint64_t k = hd + 16 * nblk + gl; k < n; k += G) store1(d + k, load8(p + k));
+}
+
+// The copying kernels' per-buffer decision: co-aligned and tiny buffers are
+// stored from the CRC path, the others by group_copy (divergent between the
+// groups of a wavefront: no cross-lane step inside).
+template <int G>
+__device__ __forceinline__ CopyTo copy_begin(const uint8_t* p, uint8_t* d, uint64_t n, uint32_t gl) {
+    CopyTo ct;
+    ct.dd = d - p;
+    ct.st = n < 64 || (ct.dd & 15) == 0;
+    if (!ct.st) group_copy<G>(p, d, n, gl);
+    return ct;
 }
 
 // CRC-32C of one buffer (seed applied) by a group of G lanes, unpipelined;
 // the result is valid on every lane of the group.
-template <int G, int U, bool LEAD = false>
+template <int G, int U, bool LEAD = false, bool COPY = false>
 __device__ __forceinline__ uint32_t buffer_crc(const uint32_t* lds, const uint8_t* p, uint64_t n, uint32_t seed,
-                                               uint32_t gl, const LaneAddr& la, bool head = true) {
+                                               uint32_t gl, const LaneAddr& la, bool head = true, CopyTo ct = {}) {
     const BufGeo g = buf_geo<G>(p, n, gl);
     BufPre<U, LEAD> pre;
     buf_preload<G, U, LEAD>(g, gl, pre);
-    const uint32_t pc = buf_body<G, U, LEAD>(lds, g, pre, seed, gl, la, head);
-    return buf_finish<G>(lds, g, pc, p, n, seed, gl, la);
+    const uint32_t pc = buf_body<G, U, LEAD, COPY>(lds, g, pre, seed, gl, la, head, ct);
+    return buf_finish<G, COPY>(lds, g, pc, p, n, seed, gl, la, ct);
 }
 
 // MSG: 0 = buffer batch, 1 = messages chained through the seed, 2 = messages
@@ -848,8 +981,12 @@ __device__ __forceinline__ uint32_t buffer_crc(const uint32_t* lds, const uint8_
 #ifndef PCRC_BATCH_OVERLAP
 #define PCRC_BATCH_OVERLAP 1
 #endif
-template <int G, int U = 4, int MSG = 0>
-__global__ __launch_bounds__(kBlock) void crc32c_batch_kernel(BatchArgs args, LaneConsts kc, PowTable pt) {
+// COPY: the copying form (photon_crc32c_copy_batch_*, photon_crc32c_gather_
+// msg_n; DESIGN.md "Copy + CRC"): the same walk, and every block is also
+// stored to the unit's destination.
+template <int G, int U = 4, int MSG = 0, bool COPY = false>
+__global__ __launch_bounds__(kBlock) void crc32c_batch_kernel(std::conditional_t<COPY, CopyBatchArgs, BatchArgs> args,
+                                                              LaneConsts kc, PowTable pt) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
     // (A/B, repo:profiles/r05t_ab_overlap_c2_c3_c4.jsonl: C2 +0.1 point 3 of 3 rounds,
     // C3 at G = 16 -0.1, C4 +-0; U = 8 spills. At G = 16 the same overlap with
@@ -895,6 +1032,10 @@ __global__ __launch_bounds__(kBlock) void crc32c_batch_kernel(BatchArgs args, La
                 s1 = args.msg_start[m + 1];
                 if (args.seeds) acc = args.seeds[m];
             }
+            uint8_t* dst = nullptr;  // COPY: where the next segment goes
+            if constexpr (COPY) {
+                if (active) dst = static_cast<uint8_t*>(args.dst[m]);
+            }
             if constexpr (MSG == 1) {
                 // No per-segment CRCs wanted: chain through the seed
                 // (crc32c_extend(seg, n, acc), Crc32Hasher::extend_hash).
@@ -906,7 +1047,14 @@ __global__ __launch_bounds__(kBlock) void crc32c_batch_kernel(BatchArgs args, La
                     // itself), so it has arrived when the next segment starts.
                     const photon_crc_iovec cur = nx;
                     nx = args.iov[sg + 1 < s1 ? sg + 1 : sg];
-                    acc = buffer_crc<G, U, kMsgLead>(lds, static_cast<const uint8_t*>(cur.base), cur.len, acc, gl, la);
+                    if constexpr (COPY) {
+                        const uint8_t* p = static_cast<const uint8_t*>(cur.base);
+                        const CopyTo ct = copy_begin<G>(p, dst, cur.len, gl);
+                        acc = buffer_crc<G, U, kMsgLead, true>(lds, p, cur.len, acc, gl, la, true, ct);
+                        dst += cur.len;
+                    } else {
+                        acc = buffer_crc<G, U, kMsgLead>(lds, static_cast<const uint8_t*>(cur.base), cur.len, acc, gl, la);
+                    }
                 }
             } else {
                 // Per-segment CRCs (seed 0) and the fold acc = acc * K ^ c,
@@ -990,19 +1138,29 @@ __global__ __launch_bounds__(kBlock) void crc32c_batch_kernel(BatchArgs args, La
                     nx = args.iov[sg + 1 < s1 ? sg + 1 : sg];
                     const uint8_t* p = static_cast<const uint8_t*>(cur.base);
                     const uint64_t n = cur.len;
+                    CopyTo ct;
+                    if constexpr (COPY) {
+                        ct = copy_begin<G>(p, dst, n, gl);
+                        dst += n;
+                    }
                     const BufGeo g = buf_geo<G>(p, n, gl);
                     BufPre<U, kMsgLead> pre;
                     buf_preload<G, U, kMsgLead>(g, gl, pre);
                     if (have) fold(cprev, nprev);
-                    const uint32_t pc = buf_body<G, U, kMsgLead>(lds, g, pre, 0u, gl, la);
-                    const uint32_t c = buf_finish<G>(lds, g, pc, p, n, 0u, gl, la);
+                    const uint32_t pc = buf_body<G, U, kMsgLead, COPY>(lds, g, pre, 0u, gl, la, true, ct);
+                    const uint32_t c = buf_finish<G, COPY>(lds, g, pc, p, n, 0u, gl, la, ct);
                     const uint32_t j = (uint32_t)((sg - s0) & (G - 1));
                     if (gl == j) pend = c;
                     if (j == G - 1 || sg + 1 == s1) {
                         const uint64_t first = sg - j;
                         // Held back, two per lane, and written when a third
                         // comes or the wave ends (see HeldStores above).
-                        if (gl <= j && !(PCRC_ABL & 8)) seg_held.put(args.out + first + gl, pend);
+                        // (COPY: stored at once -- the payload stores share
+                        // the queue anyway, and the held pairs' six registers
+                        // made the 8-lane 4-row build spill.)
+                        if constexpr (COPY) {
+                            if (gl <= j) args.out[first + gl] = pend;
+                        } else if (gl <= j && !(PCRC_ABL & 8)) seg_held.put(args.out + first + gl, pend);
                     }
                     cprev = c;
                     nprev = n;
@@ -1033,6 +1191,19 @@ __global__ __launch_bounds__(kBlock) void crc32c_batch_kernel(BatchArgs args, La
             }
             if (args.seeds) *seed = args.seeds[bi];
         }
+    };
+    // COPY: the destination of the wave's buffer wv of this lane group, and
+    // how its blocks get there (copy_begin; nothing for a group past the end)
+    auto copy_item = [&](uint64_t wv, const uint8_t* p, uint64_t n) {
+        CopyTo ct;
+        if constexpr (COPY) {
+            const uint64_t bi = wv * GPW + grp;
+            if (bi < args.count) {
+                uint8_t* dst = args.dst ? static_cast<uint8_t*>(args.dst[bi]) : args.dst_base + bi * args.dst_stride;
+                ct = copy_begin<G>(p, dst, n, gl);
+            }
+        }
+        return ct;
     };
     if constexpr (kOverlap) {
         constexpr uint32_t kVec = lds_bytes_for<G>() / 16, kPer = (kVec + kBlock - 1) / kBlock;
@@ -1073,8 +1244,11 @@ __global__ __launch_bounds__(kBlock) void crc32c_batch_kernel(BatchArgs args, La
                 buf_preload<G, U, kLead>(g, gl, pre);
             }
             const uint32_t s = args.shift_init ? 0u : seed;
-            const uint32_t pc = buf_body<G, U, kLead>(lds, g, pre, s, gl, la, !args.shift_init);
-            const uint32_t crc = buf_finish<G>(lds, g, pc, p, n, s, gl, la);
+            // COPY: a buffer that is not co-aligned is copied here, after its
+            // first rows were issued (in the prologue: across the barrier)
+            const CopyTo ct = copy_item(wv, p, n);
+            const uint32_t pc = buf_body<G, U, kLead, COPY>(lds, g, pre, s, gl, la, !args.shift_init, ct);
+            const uint32_t crc = buf_finish<G, COPY>(lds, g, pc, p, n, s, gl, la, ct);
             const uint64_t bi = wv * GPW + grp;
             if (bi < args.count && gl == 0) args.out[bi] = crc ^ args.init_shift;  // init_shift is 0 unless shift_init
         }
@@ -1087,8 +1261,9 @@ __global__ __launch_bounds__(kBlock) void crc32c_batch_kernel(BatchArgs args, La
         uint64_t n;
         uint32_t seed;
         item(wv, &p, &n, &seed);
-        const uint32_t crc = buffer_crc<G, U, kLead>(lds, p, n, args.shift_init ? 0u : seed, gl, la,
-                                                               !args.shift_init);
+        const CopyTo ct = copy_item(wv, p, n);
+        const uint32_t crc = buffer_crc<G, U, kLead, COPY>(lds, p, n, args.shift_init ? 0u : seed, gl, la,
+                                                           !args.shift_init, ct);
         if (active && gl == 0) args.out[bi] = crc ^ args.init_shift;  // init_shift is 0 unless shift_init
     }
 }
