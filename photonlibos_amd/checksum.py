@@ -264,6 +264,11 @@ def set_lanes_per_buffer(g):
     _check(lib().photon_crc_set_lanes_per_buffer(g))
 
 
+def set_batch_grid(workgroups):
+    """Workgroups of the persistent batch grids (0 = one per CU, the default)."""
+    _check(lib().photon_crc_set_batch_grid(workgroups))
+
+
 def batch_strided(base, stride, nbytes, count, out, seed=0, seeds=None, stream=None):
     """out[i] = crc32c_extend(base + i*stride, nbytes, seeds[i] or seed). Async."""
     _check(lib().photon_crc32c_batch_strided(_ptr(base), stride, nbytes, count, seed & 0xFFFFFFFF, _ptr(seeds),

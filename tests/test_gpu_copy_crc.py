@@ -120,7 +120,7 @@ def test_row_boundaries(dev_pool, oracle, g):
     _run_iov(torch, oracle, host, d, _row_cases(g, (0,)), g)
 
 
-@pytest.mark.parametrize("g", [4, 32])
+@pytest.mark.parametrize("g", [4, 8, 16, 32, 64])
 def test_not_co_aligned(dev_pool, oracle, g):
     torch, host, d = dev_pool
     _run_iov(torch, oracle, host, d, _row_cases(g, (1, 4, 8, 13)), g)
