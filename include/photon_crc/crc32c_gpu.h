@@ -312,6 +312,26 @@ int photon_crc64ecma_combine_batch(const uint64_t* d_crc1, const uint64_t* d_crc
 int photon_crc64ecma_batch_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_msg_start, uint64_t nmsg,
                                  uint64_t nseg, uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_seg_out,
                                  uint64_t* d_out, void* stream);
+/* Copy + CRC-64/ECMA in one pass: photon_crc32c_copy_batch_strided / _iov and
+ * photon_crc32c_gather_msg_n for CRC-64/ECMA, under the contract written at
+ * (iv) above (asynchronous, nothing allocated or synchronised, capturable; no
+ * byte outside [dst, dst + len) written; any alignment, one read when
+ * (dst - src) % 16 == 0). Values are crc64ecma_extend's (crc.cpp:119-122):
+ * d_out[i] / d_out[m] what photon_crc64ecma_batch_strided / _batch_iov /
+ * _batch_msg_n give for the same inputs, d_seg_out[s] (optional) =
+ * crc64ecma(seg_s, 0). An OSS multipart upload's parts assembled back to
+ * back, with a CRC per part and the object's CRC, is one gather call. */
+int photon_crc64ecma_copy_batch_strided(const void* src_base, uint64_t src_stride,
+                                        void* d_dst_base, uint64_t dst_stride,
+                                        uint64_t nbytes, uint64_t count, uint64_t seed0,
+                                        const uint64_t* d_seeds, uint64_t* d_out, void* stream);
+int photon_crc64ecma_copy_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst,
+                                    uint64_t count, uint64_t seed0, const uint64_t* d_seeds,
+                                    uint64_t* d_out, void* stream);
+int photon_crc64ecma_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_msg_start,
+                                  uint64_t nmsg, uint64_t nseg, void* const* d_dst,
+                                  uint64_t seed0, const uint64_t* d_seeds,
+                                  uint64_t* d_seg_out, uint64_t* d_out, void* stream);
 /* photon_crc32c_extend_device for CRC-64/ECMA (crc64ecma_extend, crc.cpp:
  * 119-122): the same latency path for spans up to 256 KiB (a small kernel of
  * up to 33 workgroups), one launch over the chip above, the same per-stream

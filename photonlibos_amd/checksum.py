@@ -29,6 +29,7 @@ __all__ = [
     "copy_batch_strided", "copy_batch_iov", "gather_msg_n",
     "crc64ecma", "crc64ecma_extend", "crc64ecma_sw", "crc64ecma_hw", "crc64ecma_combine", "crc64ecma_series",
     "crc64ecma_combine_series", "crc64ecma_trim",
+    "copy_batch64_strided", "copy_batch64_iov", "gather64_msg_n",
     "batch64_strided", "batch64_iov", "combine64_batch", "trim64_batch", "batch64_msg_n", "host_batch64_strided", "extend64_device", "extend_spans", "extend64_spans", "Span", "combine_batch", "fill_splitmix", "read_stream", "IOVEC_DTYPE",
 ]
 
@@ -391,6 +392,29 @@ def batch64_msg_n(iov, msg_start, nmsg, nseg, seg_out, out, seed=0, seeds=None, 
     """out[m] = crc64ecma_extend chained over message m's segments (uint64). Async."""
     _check(lib().photon_crc64ecma_batch_msg_n(_ptr(iov), _ptr(msg_start), nmsg, nseg, seed & 0xFFFFFFFFFFFFFFFF,
                                               _ptr(seeds), _ptr(seg_out), _ptr(out), _stream(stream)))
+
+
+def copy_batch64_strided(src, src_stride, dst, dst_stride, nbytes, count, out, seed=0, seeds=None, stream=None):
+    """copy_batch_strided for CRC-64/ECMA: dst + i*dst_stride receives the nbytes at
+    src + i*src_stride, out[i] = crc64ecma_extend of them (uint64 seeds / out). Async."""
+    _check(lib().photon_crc64ecma_copy_batch_strided(_ptr(src), src_stride, _ptr(dst), dst_stride, nbytes, count,
+                                                     seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(out),
+                                                     _stream(stream)))
+
+
+def copy_batch64_iov(src_iov, dst_ptrs, count, out, seed=0, seeds=None, stream=None):
+    """copy_batch_iov for CRC-64/ECMA: dst_ptrs[i] receives src_iov[i]'s bytes, out[i] =
+    crc64ecma_extend(src_i, len_i, seed_i) (uint64). Async."""
+    _check(lib().photon_crc64ecma_copy_batch_iov(_ptr(src_iov), _ptr(dst_ptrs), count, seed & 0xFFFFFFFFFFFFFFFF,
+                                                 _ptr(seeds), _ptr(out), _stream(stream)))
+
+
+def gather64_msg_n(iov, msg_start, nmsg, nseg, dst_ptrs, seg_out, out, seed=0, seeds=None, stream=None):
+    """batch64_msg_n that also gathers: message m's segments (an object's parts) are
+    written back to back at dst_ptrs[m]; seg_out (optional) = crc64ecma per segment. Async."""
+    _check(lib().photon_crc64ecma_gather_msg_n(_ptr(iov), _ptr(msg_start), nmsg, nseg, _ptr(dst_ptrs),
+                                               seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(seg_out), _ptr(out),
+                                               _stream(stream)))
 
 
 def extend64_device(data, nbytes, out, seed=0, stream=None):

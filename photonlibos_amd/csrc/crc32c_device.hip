@@ -624,6 +624,47 @@ int launch_batch64(const Batch64Args& a, uint64_t typical_len, hipStream_t strea
     return 0;
 }
 
+// The CRC-64 copying kernels (crc64_batch_kernel<G, true>, crc64_gather_kernel<G>;
+// DESIGN.md §4.4): always the generic kernel, one build per lane-group size
+// (photon_crc_set_lanes_per_buffer and photon_crc_set_batch_grid apply; the
+// full-row kernel has no copying form). gather: units = messages.
+int launch_copy64(const CopyBatch64Args& a, bool gather, uint64_t units, int g, hipStream_t stream) {
+    if (units == 0) return 0;
+#if PCRC64_ABL != 0 || PCRC64_ROLL != 1 || PCRC64_U != 2
+    // A/B builds of the row loop: the copying kernels exist for the product's loop only
+    return fail(-ENOTSUP, "the copying CRC-64 kernels are not part of this A/B build");
+#else
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint64_t gpw = 64 / g;
+    const uint64_t waves = (units + gpw - 1) / gpw;
+    uint64_t grid = (waves + kWaves - 1) / kWaves;
+    if (grid > (uint64_t)cus) grid = cus;
+    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
+    const LaneConsts64& kc = lane_consts64(g);
+    HeavyLaunch heavy(stream);
+#define LC64(GG)                                                                                                \
+    do {                                                                                                        \
+        if (gather)                                                                                             \
+            hipLaunchKernelGGL((crc64_gather_kernel<GG>), dim3(grid), dim3(kBlock), 0, stream, a, kc);          \
+        else                                                                                                    \
+            hipLaunchKernelGGL((crc64_batch_kernel<GG, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc);     \
+    } while (0)
+    switch (g) {
+        case 64: LC64(64); break;
+        case 32: LC64(32); break;
+        case 16: LC64(16); break;
+        case 8: LC64(8); break;
+        default: LC64(4); break;
+    }
+#undef LC64
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, gather ? "crc64_gather_kernel launch" : "crc64_batch_kernel<copy> launch");
+    return 0;
+#endif
+}
+
 // Host-memory pipeline (photon_crc32c_host_batch_strided): per device, a copy
 // stream and a compute stream, kNumStage device staging chunks. Chunk i is
 // copied (H2D, 2-D so any host stride packs densely) while chunk i-1 is
@@ -1727,6 +1768,74 @@ int photon_crc64ecma_batch_msg_n(const photon_crc_iovec* d_iov, const uint64_t* 
     if (scratch) {
         const int frc = scratch_free(scratch, st);
         if (!rc) rc = frc;
+    }
+    return rc;
+}
+
+// Copy + CRC-64/ECMA in one pass (crc32c_gpu.h).
+int photon_crc64ecma_copy_batch_strided(const void* src_base, uint64_t src_stride, void* d_dst_base,
+                                        uint64_t dst_stride, uint64_t nbytes, uint64_t count, uint64_t seed0,
+                                        const uint64_t* d_seeds, uint64_t* d_out, void* stream) {
+    if (!count) return 0;
+    if (!d_out || ((!src_base || !d_dst_base) && nbytes)) return fail(-EINVAL, "null source, destination or output");
+    CopyBatch64Args a{};
+    a.base = static_cast<const uint8_t*>(src_base);
+    a.stride = src_stride;
+    a.nbytes = nbytes;
+    a.count = count;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.seed0 = seed0;
+    a.dst_base = static_cast<uint8_t*>(d_dst_base);
+    a.dst_stride = dst_stride;
+    if (PCRC64_SHIFT_INIT && !d_seeds && !(reinterpret_cast<uintptr_t>(src_base) & 15) && !(src_stride & 15) &&
+        nbytes >= 64) {
+        a.shift_init = 1;
+        a.init_shift = mulmod64(~seed0, xpow64(8ull * nbytes));
+    }
+    return launch_copy64(a, false, count, choose_lanes(nbytes), static_cast<hipStream_t>(stream));
+}
+
+int photon_crc64ecma_copy_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t count,
+                                    uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out, void* stream) {
+    if (!count) return 0;
+    if (!d_src || !d_dst || !d_out) return fail(-EINVAL, "null descriptor array, destination array or output");
+    CopyBatch64Args a{};
+    a.iov = d_src;
+    a.count = count;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.seed0 = seed0;
+    a.dst = d_dst;
+    return launch_copy64(a, false, count, choose_lanes(65536), static_cast<hipStream_t>(stream));
+}
+
+int photon_crc64ecma_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_msg_start, uint64_t nmsg,
+                                  uint64_t nseg, void* const* d_dst, uint64_t seed0, const uint64_t* d_seeds,
+                                  uint64_t* d_seg_out, uint64_t* d_out, void* stream) {
+    if (!nmsg) return 0;
+    if (!d_msg_start || !d_dst || !d_out || (!d_iov && nseg)) return fail(-EINVAL, "null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // One payload-reading kernel (a lane group walks its message's segments
+    // and keeps the running destination). Without d_seg_out it chains the
+    // register and writes d_out; with it, the segment CRCs are folded by
+    // crc64_msg_fold_kernel as in photon_crc64ecma_batch_msg_n. No scratch.
+    CopyBatch64Args a{};
+    a.iov = d_iov;
+    a.count = nseg;
+    a.out = d_out;
+    a.seg_out = d_seg_out;
+    a.msg_start = d_msg_start;
+    a.nmsg = nmsg;
+    a.seeds = d_seeds;
+    a.seed0 = seed0;
+    a.dst = d_dst;
+    int rc = launch_copy64(a, true, nmsg, choose_lanes(8192), st);
+    if (!rc && d_seg_out) {
+        hipLaunchKernelGGL(crc64_msg_fold_kernel, dim3((nmsg + 255) / 256), dim3(256), 0, st, d_iov, d_msg_start,
+                           nmsg, d_seg_out, seed0, d_seeds, d_out, pow_table64());
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = hip_fail(e, "crc64_msg_fold_kernel launch");
     }
     return rc;
 }

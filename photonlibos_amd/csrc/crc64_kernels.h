@@ -109,6 +109,21 @@ struct Batch64Args {
     uint32_t shift_init;
 };
 
+// The copying kernels (crc64_batch_kernel<G, true>, crc64_gather_kernel<G>;
+// DESIGN.md §4.4): where unit i's bytes go, as CopyBatchArgs. Buffer batches:
+// dst[i], or dst_base + i*dst_stride when dst is null. Gather: unit m =
+// message m, segments iov[msg_start[m] .. msg_start[m+1]) back to back at
+// dst[m]; seg_out (optional) = per-segment CRCs (seed 0), then out[] is left
+// to crc64_msg_fold_kernel; without it out[m] = the CRC chained from seed_m.
+struct CopyBatch64Args : Batch64Args {
+    uint8_t* dst_base;
+    uint64_t dst_stride;
+    void* const* dst;
+    const uint64_t* msg_start;
+    uint64_t nmsg;
+    uint64_t* seg_out;
+};
+
 __device__ __forceinline__ uint2 lds_u2(const uint32_t* lds, uint32_t byte_addr) {
     return *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(lds) + byte_addr);
 }
@@ -432,16 +447,39 @@ __device__ __forceinline__ uint64_t finish_xor16(uint2 q, uint32_t d, const uint
 // The raw CRC-64 register after the bytes [p, p+n) from `init` (a group of
 // G lanes; valid on the group's first lane; crc64ecma_extend = ~reg with
 // init = ~crc, crc.cpp:119-122).
-template <int G>
+// COPY (the copying kernels): every 16-byte block a lane takes
+// into the CRC is also stored at the same offset from the destination's
+// aligned start (ct.dd, a multiple of 16 when ct.st), from the register the
+// CRC reads and under the condition that lets it into the CRC. The tiny
+// buffer's and the tail's bytes are walked by the group's first lane alone,
+// which stores each byte as it loads it.
+template <int G, bool COPY = false>
 __device__ __forceinline__ uint64_t buffer_reg64(const uint32_t* lds, const uint8_t* p, uint64_t n, uint64_t init,
                                                  uint32_t gl, uint32_t lane, const LaneAddr64& la,
-                                                 bool head = true) {
+                                                 bool head = true, CopyTo ct = {}) {
+    static_assert(!COPY || (PCRC64_ABL == 0 && PCRC64_ROLL == 1 && PCRC64_U == 2),
+                  "the copying kernels are built with the product's row loop only");
     constexpr int U = PCRC64_U;
+    // COPY: the byte / block read at source address q, to the destination
+    auto put1 = [&](const uint8_t* q, uint8_t b) {
+        if constexpr (COPY) {
+            if (ct.st) store1(const_cast<uint8_t*>(q) + ct.dd, b);
+        }
+    };
+    auto put16 = [&](const uint8_t* q, const uint4& v) {
+        if constexpr (COPY) {
+            if (ct.st) store16(const_cast<uint8_t*>(q) + ct.dd, v);
+        }
+    };
     uint64_t reg;
     if (n < 64) {
         reg = init;
         if (gl == 0)
-            for (uint64_t k = 0; k < n; ++k) reg = bytestep64(lds, reg, load8(p + k), la);
+            for (uint64_t k = 0; k < n; ++k) {
+                const uint8_t b = load8(p + k);
+                put1(p + k, b);
+                reg = bytestep64(lds, reg, b, la);
+            }
     } else {
         const uint8_t* a0 = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(p) & ~uintptr_t(15));
         const uint8_t* e = p + n;
@@ -472,6 +510,16 @@ __device__ __forceinline__ uint64_t buffer_reg64(const uint32_t* lds, const uint
         // Row 0 (head: masked leading bytes + inverted init).
         if (gl < nb) {
             uint4 w = w0;
+            if constexpr (COPY) {
+                // the RAW block (w below is masked and mixed with the init on
+                // lanes 0 and 1); block 0 of a buffer that starts inside it
+                // by narrow stores, bytes s0..15 only
+                if (ct.st) {
+                    uint8_t* d = const_cast<uint8_t*>(lp) + ct.dd;
+                    if (gl == 0 && s0) store_head(d, w0, s0);
+                    else store16(d, w0);
+                }
+            }
             if (head && !(PCRC64_ABL & 1) && gl < 2) {  // head == false: aligned, init 0
                 const uint64_t lo = head_word64(((uint64_t)w.y << 32) | w.x, (int)gl * 16, s0, init);
                 const uint64_t hi = head_word64(((uint64_t)w.w << 32) | w.z, (int)gl * 16 + 8, s0, init);
@@ -481,13 +529,20 @@ __device__ __forceinline__ uint64_t buffer_reg64(const uint32_t* lds, const uint
         }
 #pragma unroll
         for (int u = 0; u < U - 1; ++u)
-            if ((uint32_t)u < lead) pc = sstep64(lds, pc, la, lag16_64(lds, wl[u], la));
+            if ((uint32_t)u < lead) {
+                put16(lp + (1 + u) * (16 * G), wl[u]);
+                pc = sstep64(lds, pc, la, lag16_64(lds, wl[u], la));
+            }
         uint64_t row = 1 + lead;
         // U lagged blocks (independent) then U row shifts (the carried chain).
-        auto column_step = [&](const uint4(&w)[U]) {
+        // `r`: the first of the U rows (COPY: where they are stored from here).
+        auto column_step = [&](const uint4(&w)[U], uint64_t r) {
             uint2 c[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) c[u] = lag16_64(lds, w[u], la);
+            for (int u = 0; u < U; ++u) {
+                put16(lp + (r + u) * (16 * G), w[u]);
+                c[u] = lag16_64(lds, w[u], la);
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) pc = sstep64(lds, pc, la, c[u]);
         };
@@ -495,11 +550,13 @@ __device__ __forceinline__ uint64_t buffer_reg64(const uint32_t* lds, const uint
             for (; row + 2 * U <= full; row += U) {
                 if constexpr (PCRC64_ROLL) {
                     // each row's registers reloaded as soon as its lagged
-                    // block is taken: no copies on the loop edge
+                    // block is taken: no copies on the loop edge (COPY: the
+                    // row is stored before the reload overwrites it)
                     uint2 c[U];
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         c[u] = lag16_64(lds, cur[u], la);
+                        put16(lp + (row + u) * (16 * G), cur[u]);
                         cur[u] = load16(lp + (row + U + u) * (16 * G));
                     }
 #pragma unroll
@@ -508,14 +565,17 @@ __device__ __forceinline__ uint64_t buffer_reg64(const uint32_t* lds, const uint
                     uint4 nxt[U];
 #pragma unroll
                     for (int u = 0; u < U; ++u) nxt[u] = load16(lp + (row + U + u) * (16 * G));
-                    column_step(cur);
+                    column_step(cur, row);
 #pragma unroll
                     for (int u = 0; u < U; ++u) cur[u] = nxt[u];
                 }
             }
-            column_step(cur);
+            column_step(cur, row);
         }
-        if (part) pc = sstep64(lds, pc, la, lag16_64(lds, wp, la));
+        if (part) {
+            put16(lp + full * (16 * G), wp);
+            pc = sstep64(lds, pc, la, lag16_64(lds, wp, la));
+        }
         // Q * x^(64 + 128 d) (Q -> P and the shift to the end of the blocks), XOR over the group.
         const uint32_t d = (rlast + G - 1 - gl) & (G - 1);
         if constexpr (G == 16 && PCRC64_FIN16 && !(PCRC64_ABL & 6)) {
@@ -525,7 +585,11 @@ __device__ __forceinline__ uint64_t buffer_reg64(const uint32_t* lds, const uint
             reg = (PCRC64_ABL & 4) ? f : ((uint64_t)group_xor<G>((uint32_t)(f >> 32)) << 32) | group_xor<G>((uint32_t)f);
         }
         if (gl == 0)
-            for (const uint8_t* q = eb; q < e; ++q) reg = bytestep64(lds, reg, load8(q), la);
+            for (const uint8_t* q = eb; q < e; ++q) {
+                const uint8_t b = load8(q);
+                put1(q, b);
+                reg = bytestep64(lds, reg, b, la);
+            }
     }
     return reg;
 }
@@ -545,9 +609,11 @@ __device__ __forceinline__ void stamp64_write(uint64_t* t, const uint64_t (&v)[5
 
 // Any pointer / length / seed (iovec batches, ragged and unaligned buffers).
 // STAMP (probe builds): t0, tables built, first buffer done, loop done, end.
-template <int G, bool STAMP = false>
-__device__ __forceinline__ void crc64_batch_run(const Batch64Args& args, const LaneConsts64& kc, uint32_t* lds,
-                                                uint64_t* t) {
+// COPY: the copying form (photon_crc64ecma_copy_batch_*): the
+// same walk, and every block is also stored to the buffer's destination.
+template <int G, bool STAMP = false, bool COPY = false>
+__device__ __forceinline__ void crc64_batch_run(const std::conditional_t<COPY, CopyBatch64Args, Batch64Args>& args,
+                                                const LaneConsts64& kc, uint32_t* lds, uint64_t* t) {
     uint64_t ts[5] = {0, 0, 0, 0, 0};
     if constexpr (STAMP) ts[0] = __builtin_amdgcn_s_memrealtime();
     load_tables64<G>(lds, kc);
@@ -574,9 +640,19 @@ __device__ __forceinline__ void crc64_batch_run(const Batch64Args& args, const L
             }
             if (args.seeds) seed = args.seeds[bi];
         }
+        // COPY: how the buffer's blocks get to its destination (copy_begin;
+        // nothing for a group past the end of the batch)
+        CopyTo ct;
+        if constexpr (COPY) {
+            if (active) {
+                uint8_t* dst = args.dst ? static_cast<uint8_t*>(args.dst[bi]) : args.dst_base + bi * args.dst_stride;
+                ct = copy_begin<G>(p, dst, n, gl);
+            }
+        }
         // crc.cpp:119-122: the register starts at ~crc and the result is inverted
-        const uint64_t reg = args.shift_init ? buffer_reg64<G>(lds, p, n, 0ull, gl, lane, la, false) ^ args.init_shift
-                                             : buffer_reg64<G>(lds, p, n, ~seed, gl, lane, la);
+        const uint64_t reg = args.shift_init
+                                 ? buffer_reg64<G, COPY>(lds, p, n, 0ull, gl, lane, la, false, ct) ^ args.init_shift
+                                 : buffer_reg64<G, COPY>(lds, p, n, ~seed, gl, lane, la, true, ct);
         if (active && gl == 0) args.out[bi] = ~reg;
         if constexpr (STAMP) {
             if (ts[2] == 0) ts[2] = __builtin_amdgcn_s_memrealtime();
@@ -589,10 +665,61 @@ __device__ __forceinline__ void crc64_batch_run(const Batch64Args& args, const L
     }
 }
 
-template <int G>
-__global__ __launch_bounds__(kBlock) void crc64_batch_kernel(Batch64Args args, LaneConsts64 kc) {
+template <int G, bool COPY = false>
+__global__ __launch_bounds__(kBlock) void crc64_batch_kernel(std::conditional_t<COPY, CopyBatch64Args, Batch64Args> args,
+                                                             LaneConsts64 kc) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
-    crc64_batch_run<G>(args, kc, lds, nullptr);
+    crc64_batch_run<G, false, COPY>(args, kc, lds, nullptr);
+}
+
+// photon_crc64ecma_gather_msg_n: one lane group per message
+// walks its segments, lands them back to back at dst[m] (the running
+// destination is carried: no prefix sum) and checksums them from the same
+// read. Without seg_out the raw register is chained from segment to segment
+// (crc64ecma_extend, seg after seg): buffer_reg64's result is valid on the
+// group's first lane only while the next head takes the init on lanes 0 and
+// 1, so it is broadcast within the group. With seg_out every segment starts
+// from ~0 and its CRC is stored at once; crc64_msg_fold_kernel then folds
+// them into out[] (it reads no payload).
+template <int G>
+__global__ __launch_bounds__(kBlock) void crc64_gather_kernel(CopyBatch64Args args, LaneConsts64 kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
+    load_tables64<G>(lds, kc);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    constexpr int GPW = 64 / G;
+    const LaneAddr64 la = lane_addr64(lane);
+    const bool per_seg = args.seg_out != nullptr;  // uniform
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave_id(); wv * GPW < args.nmsg; wv += nwaves) {
+        const uint64_t m = wv * GPW + grp;
+        const bool active = m < args.nmsg;
+        uint64_t s0 = 0, s1 = 0, seed = args.seed0;
+        uint8_t* dst = nullptr;  // where the next segment goes
+        if (active) {
+            s0 = args.msg_start[m];
+            s1 = args.msg_start[m + 1];
+            if (args.seeds) seed = args.seeds[m];
+            dst = static_cast<uint8_t*>(args.dst[m]);
+        }
+        uint64_t reg = ~seed;  // crc.cpp:119-122
+        for (uint64_t sg = s0; sg < s1; ++sg) {
+            const uint8_t* p = static_cast<const uint8_t*>(args.iov[sg].base);
+            const uint64_t n = args.iov[sg].len;
+            const CopyTo ct = copy_begin<G>(p, dst, n, gl);
+            dst += n;
+            const uint64_t r = buffer_reg64<G, true>(lds, p, n, per_seg ? ~0ull : reg, gl, lane, la, true, ct);
+            if (per_seg) {
+                if (gl == 0) args.seg_out[sg] = ~r;
+            } else {
+                const uint64_t v = gl == 0 ? r : 0ull;
+                reg = ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+            }
+        }
+        if (!per_seg && active && gl == 0) args.out[m] = ~reg;
+    }
 }
 
 // ------------------------------------------------ full-row uniform batches

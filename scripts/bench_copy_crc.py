@@ -20,6 +20,10 @@ the ratio (b)/(a), and the spread between the alternations of each arm;
                     per launch over the payload (FETCH_SIZE counts half the
                     bytes of wide reads on gfx950, see summarize_profile.py;
                     both scalings are printed)
+  --crc64 : the same A/B, runs and summary for CRC-64/ECMA
+                    (photon_crc64ecma_batch_strided after the copy against
+                    photon_crc64ecma_copy_batch_strided); adds "margin_over_spread"
+                    = ((a) - (b)) / the larger spread and "faster_3x" (margin > 3)
 """
 import argparse
 import csv
@@ -39,6 +43,7 @@ ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--out", help="also write the JSON lines to this file")
 ap.add_argument("--pmc-run")
 ap.add_argument("--pmc-summary")
+ap.add_argument("--crc64", action="store_true")
 args = ap.parse_args()
 
 
@@ -47,7 +52,7 @@ def pmc_summary(d):
     for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         with open(f) as fh:
             for r in csv.DictReader(fh):
-                if "crc32c_batch_kernel" in r["Kernel_Name"]:
+                if ("crc64_batch_kernel" if args.crc64 else "crc32c_batch_kernel") in r["Kernel_Name"]:
                     per.setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
     nbytes, count = SHAPES["c2"]
     payload = nbytes * count
@@ -81,11 +86,12 @@ st = torch.cuda.current_stream()
 
 def arm_pair(src, dst, nbytes, count, out):
     ck._check(lib().photon_crc_memcpy_async(dst.data_ptr(), src.data_ptr(), nbytes * count, st.cuda_stream))
-    ck.batch_strided(dst, nbytes, nbytes, count, out, stream=st)
+    (ck.batch64_strided if args.crc64 else ck.batch_strided)(dst, nbytes, nbytes, count, out, stream=st)
 
 
 def arm_fused(src, dst, nbytes, count, out):
-    ck.copy_batch_strided(src, nbytes, dst, nbytes, nbytes, count, out, stream=st)
+    (ck.copy_batch64_strided if args.crc64 else ck.copy_batch_strided)(src, nbytes, dst, nbytes, nbytes, count, out,
+                                                                       stream=st)
 
 
 def bench(shape):
@@ -93,7 +99,7 @@ def bench(shape):
     src = torch.empty(nbytes * count, dtype=torch.uint8, device="cuda")
     dst = torch.zeros(nbytes * count, dtype=torch.uint8, device="cuda")
     ck.fill_splitmix(src, nbytes, nbytes, count, 0x5EED0001)
-    out = torch.zeros(count, dtype=torch.int32, device="cuda")
+    out = torch.zeros(count, dtype=torch.int64 if args.crc64 else torch.int32, device="cuda")
     if args.pmc_run:
         for _ in range(3):
             arm_fused(src, dst, nbytes, count, out)
@@ -137,6 +143,11 @@ def bench(shape):
     res["ratio_fused_over_pair"] = round(res["fused"]["ms_mean"] / res["pair"]["ms_mean"], 4)
     res["faster"] = bool(res["pair"]["ms_mean"] - res["fused"]["ms_mean"] >
                          max(res["pair"]["spread_ms"], res["fused"]["spread_ms"]))
+    if args.crc64:
+        res["crc"] = "crc64ecma"
+        spread = max(res["pair"]["spread_ms"], res["fused"]["spread_ms"])
+        res["margin_over_spread"] = round((res["pair"]["ms_mean"] - res["fused"]["ms_mean"]) / max(spread, 1e-9), 2)
+        res["faster_3x"] = bool(res["margin_over_spread"] > 3)
     return res
 
 
