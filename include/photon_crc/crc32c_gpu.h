@@ -174,6 +174,34 @@ int photon_crc32c_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_
                                uint32_t seed0, const uint32_t* d_seeds,
                                uint32_t* d_seg_out, uint32_t* d_out, void* stream);
 
+/* iovector_view::memcpy_iov (common/iovector.cpp:301-318) + the checksum in
+ * one pass: copy between two iovectors whose segment boundaries are unrelated.
+ * Message m has source segments d_src[d_src_start[m] .. d_src_start[m+1]) and
+ * destination segments d_dst[d_dst_start[m] .. d_dst_start[m+1]); both start
+ * arrays have nmsg + 1 entries, nsrc / ndst are the totals. With size_m =
+ * d_size ? d_size[m] : unlimited, k_m = min(size_m, sum of dst lengths, sum of
+ * src lengths) bytes are copied, byte j of the source stream to byte j of
+ * the destination stream; zero-length segments on either side are skipped
+ * (their base may be null). d_out[m] = crc32c_extend over exactly those k_m
+ * source bytes from seed_m (the seed when k_m == 0); d_copied[m] = k_m when
+ * d_copied is non-NULL. Destination bytes past k_m are not written, source
+ * segments past k_m are not read. memcpy_to (one destination segment: the
+ * gather above), memcpy_from (scatter: ONE SOURCE SEGMENT per message) and
+ * any re-segmentation are special cases.
+ * Contract (iv): a null d_src_start, d_dst_start or d_out, a null d_src with
+ * nsrc > 0 or a null d_dst with ndst > 0 give -EINVAL. No byte outside a
+ * destination segment is written and nothing is read-modify-written, so
+ * destination segments may sit back to back at odd addresses. The alignment
+ * rule holds per piece (a run of bytes inside one source and one destination
+ * segment): a piece with (dst - src) % 16 == 0 is read once, any other is
+ * copied first and checksummed from the cache. No per-segment CRCs: a piece
+ * is in general neither a source nor a destination segment. */
+int photon_crc32c_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                 const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                 uint64_t nmsg, const uint64_t* d_size,
+                                 uint32_t seed0, const uint32_t* d_seeds,
+                                 uint32_t* d_out, uint64_t* d_copied, void* stream);
+
 /* d_out[i] = crc32c_combine(d_crc1[i], d_crc2[i], d_len2[i]) with the
  * reference's shortcuts (crc1 == 0 -> crc2, len2 == 0 -> crc1). */
 int photon_crc32c_combine_batch(const uint32_t* d_crc1, const uint32_t* d_crc2, const uint32_t* d_len2,
@@ -332,6 +360,13 @@ int photon_crc64ecma_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t*
                                   uint64_t nmsg, uint64_t nseg, void* const* d_dst,
                                   uint64_t seed0, const uint64_t* d_seeds,
                                   uint64_t* d_seg_out, uint64_t* d_out, void* stream);
+/* photon_crc32c_copy_msg_iov_n for CRC-64/ECMA: the same arguments, walk and
+ * contract; d_out[m] = crc64ecma_extend over the k_m copied bytes from seed_m. */
+int photon_crc64ecma_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                    const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                    uint64_t nmsg, const uint64_t* d_size,
+                                    uint64_t seed0, const uint64_t* d_seeds,
+                                    uint64_t* d_out, uint64_t* d_copied, void* stream);
 /* photon_crc32c_extend_device for CRC-64/ECMA (crc64ecma_extend, crc.cpp:
  * 119-122): the same latency path for spans up to 256 KiB (a small kernel of
  * up to 33 workgroups), one launch over the chip above, the same per-stream

@@ -30,6 +30,7 @@ __all__ = [
     "crc64ecma", "crc64ecma_extend", "crc64ecma_sw", "crc64ecma_hw", "crc64ecma_combine", "crc64ecma_series",
     "crc64ecma_combine_series", "crc64ecma_trim",
     "copy_batch64_strided", "copy_batch64_iov", "gather64_msg_n",
+    "copy_msg_iov_n", "copy_msg64_iov_n",
     "batch64_strided", "batch64_iov", "combine64_batch", "trim64_batch", "batch64_msg_n", "host_batch64_strided", "extend64_device", "extend_spans", "extend64_spans", "Span", "combine_batch", "fill_splitmix", "read_stream", "IOVEC_DTYPE",
 ]
 
@@ -415,6 +416,26 @@ def gather64_msg_n(iov, msg_start, nmsg, nseg, dst_ptrs, seg_out, out, seed=0, s
     _check(lib().photon_crc64ecma_gather_msg_n(_ptr(iov), _ptr(msg_start), nmsg, nseg, _ptr(dst_ptrs),
                                                seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(seg_out), _ptr(out),
                                                _stream(stream)))
+
+
+def copy_msg_iov_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nmsg, out, size=None, seed=0, seeds=None,
+                   copied=None, stream=None):
+    """iovector_view::memcpy_iov + CRC-32C: message m's source segments
+    src_iov[src_start[m]:src_start[m+1]] are copied as one byte stream into its
+    destination segments dst_iov[dst_start[m]:dst_start[m+1]], at most size[m]
+    bytes (no cap without size); out[m] = crc32c_extend over the copied bytes
+    from seed_m, copied[m] (optional, uint64) = their count. Async."""
+    _check(lib().photon_crc32c_copy_msg_iov_n(_ptr(src_iov), _ptr(src_start), nsrc, _ptr(dst_iov), _ptr(dst_start),
+                                              ndst, nmsg, _ptr(size), seed & 0xFFFFFFFF, _ptr(seeds), _ptr(out),
+                                              _ptr(copied), _stream(stream)))
+
+
+def copy_msg64_iov_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nmsg, out, size=None, seed=0, seeds=None,
+                     copied=None, stream=None):
+    """copy_msg_iov_n for CRC-64/ECMA (uint64 seeds / out). Async."""
+    _check(lib().photon_crc64ecma_copy_msg_iov_n(_ptr(src_iov), _ptr(src_start), nsrc, _ptr(dst_iov),
+                                                 _ptr(dst_start), ndst, nmsg, _ptr(size), seed & 0xFFFFFFFFFFFFFFFF,
+                                                 _ptr(seeds), _ptr(out), _ptr(copied), _stream(stream)))
 
 
 def extend64_device(data, nbytes, out, seed=0, stream=None):

@@ -538,6 +538,34 @@ int launch_copy(const CopyBatchArgs& a, int msg, uint64_t units, int g, hipStrea
     return 0;
 }
 
+// crc32c_copy_iov_kernel<G, U>: one build per lane-group
+// size with the default rows per step of that size, grid as launch_copy.
+int launch_copy_iov(const CopyIovArgs& a, int g, hipStream_t stream) {
+    if (a.nmsg == 0) return 0;
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint64_t gpw = 64 / g;
+    const uint64_t waves = (a.nmsg + gpw - 1) / gpw;
+    uint64_t grid = (waves + kWaves - 1) / kWaves;
+    if (grid > (uint64_t)cus) grid = cus;
+    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
+    const LaneConsts& kc = lane_consts(g);
+    HeavyLaunch heavy(stream);
+#define LCI(GG, UU) hipLaunchKernelGGL((crc32c_copy_iov_kernel<GG, UU>), dim3(grid), dim3(kBlock), 0, stream, a, kc)
+    switch (g) {
+        case 64: LCI(64, 4); break;
+        case 32: LCI(32, 4); break;
+        case 16: LCI(16, 2); break;
+        case 8: LCI(8, 4); break;
+        default: LCI(4, 4); break;
+    }
+#undef LCI
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "crc32c_copy_iov_kernel launch");
+    return 0;
+}
+
 LaneConsts64 make_lane_consts64(int g) {
     LaneConsts64 c;
     c.kshift = xpow64(8ull * 16ull * (uint64_t)g);
@@ -661,6 +689,35 @@ int launch_copy64(const CopyBatch64Args& a, bool gather, uint64_t units, int g, 
 #undef LC64
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, gather ? "crc64_gather_kernel launch" : "crc64_batch_kernel<copy> launch");
+    return 0;
+#endif
+}
+
+// crc64_copy_iov_kernel<G>, as launch_copy64.
+int launch_copy_iov64(const CopyIov64Args& a, int g, hipStream_t stream) {
+    if (a.nmsg == 0) return 0;
+#if PCRC64_ABL != 0 || PCRC64_ROLL != 1 || PCRC64_U != 2
+    return fail(-ENOTSUP, "the copying CRC-64 kernels are not part of this A/B build");
+#else
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint64_t gpw = 64 / g;
+    const uint64_t waves = (a.nmsg + gpw - 1) / gpw;
+    uint64_t grid = (waves + kWaves - 1) / kWaves;
+    if (grid > (uint64_t)cus) grid = cus;
+    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
+    const LaneConsts64& kc = lane_consts64(g);
+    HeavyLaunch heavy(stream);
+    switch (g) {
+        case 64: hipLaunchKernelGGL(crc64_copy_iov_kernel<64>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
+        case 32: hipLaunchKernelGGL(crc64_copy_iov_kernel<32>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
+        case 16: hipLaunchKernelGGL(crc64_copy_iov_kernel<16>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
+        case 8: hipLaunchKernelGGL(crc64_copy_iov_kernel<8>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
+        default: hipLaunchKernelGGL(crc64_copy_iov_kernel<4>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "crc64_copy_iov_kernel launch");
     return 0;
 #endif
 }
@@ -1683,6 +1740,28 @@ int photon_crc32c_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_
     return launch_copy(a, d_seg_out ? 2 : 1, nmsg, choose_lanes(8192), static_cast<hipStream_t>(stream));
 }
 
+int photon_crc32c_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                 const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                 uint64_t nmsg, const uint64_t* d_size, uint32_t seed0, const uint32_t* d_seeds,
+                                 uint32_t* d_out, uint64_t* d_copied, void* stream) {
+    if (!nmsg) return 0;
+    if (!d_src_start || !d_dst_start || !d_out || (!d_src && nsrc) || (!d_dst && ndst))
+        return fail(-EINVAL, "null argument");
+    // Lane groups as the gather takes (choose_lanes(8192)).
+    CopyIovArgs a{};
+    a.src = d_src;
+    a.src_start = d_src_start;
+    a.dst = d_dst;
+    a.dst_start = d_dst_start;
+    a.nmsg = nmsg;
+    a.size = d_size;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.copied = d_copied;
+    a.seed0 = seed0;
+    return launch_copy_iov(a, choose_lanes(8192), static_cast<hipStream_t>(stream));
+}
+
 int photon_crc64ecma_batch_strided(const void* d_base, uint64_t stride, uint64_t nbytes, uint64_t count,
                                    uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out, void* stream) {
     if (count && (!d_out || (!d_base && nbytes))) return fail(-EINVAL, "null buffer or output");
@@ -1838,6 +1917,27 @@ int photon_crc64ecma_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t*
         if (e != hipSuccess) rc = hip_fail(e, "crc64_msg_fold_kernel launch");
     }
     return rc;
+}
+
+int photon_crc64ecma_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                    const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                    uint64_t nmsg, const uint64_t* d_size, uint64_t seed0, const uint64_t* d_seeds,
+                                    uint64_t* d_out, uint64_t* d_copied, void* stream) {
+    if (!nmsg) return 0;
+    if (!d_src_start || !d_dst_start || !d_out || (!d_src && nsrc) || (!d_dst && ndst))
+        return fail(-EINVAL, "null argument");
+    CopyIov64Args a{};
+    a.src = d_src;
+    a.src_start = d_src_start;
+    a.dst = d_dst;
+    a.dst_start = d_dst_start;
+    a.nmsg = nmsg;
+    a.size = d_size;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.copied = d_copied;
+    a.seed0 = seed0;
+    return launch_copy_iov64(a, choose_lanes(8192), static_cast<hipStream_t>(stream));
 }
 
 int photon_crc64ecma_extend_device(const void* d_data, uint64_t nbytes, uint64_t seed, uint64_t* d_out,

@@ -1268,6 +1268,119 @@ __global__ __launch_bounds__(kBlock) void crc32c_batch_kernel(std::conditional_t
     }
 }
 
+// photon_crc32c_copy_msg_iov_n: copy + CRC between two
+// iovectors per message (iovector_view::memcpy_iov, iovector.cpp:301-318).
+// Message m: source segments src[src_start[m] .. src_start[m+1]), destination
+// segments dst[dst_start[m] .. dst_start[m+1]), at most size[m] bytes (no
+// size array: no cap). out[m] = the CRC of the copied bytes chained from
+// seed_m, copied[m] (optional) = their count.
+struct CopyIovArgs {
+    const photon_crc_iovec* src;
+    const uint64_t* src_start;
+    const photon_crc_iovec* dst;
+    const uint64_t* dst_start;
+    uint64_t nmsg;
+    const uint64_t* size;      // optional
+    const uint32_t* seeds;     // optional
+    uint32_t* out;
+    uint64_t* copied;          // optional
+    uint32_t seed0;
+};
+
+// One side of the two-cursor walk: the current segment's unconsumed part
+// [p, p + rem). PF: the NEXT segment's descriptor is loaded when the current
+// one is taken -- before the rows of the piece(s) that consume it, as the
+// message kernels prefetch theirs (the last one re-reads itself). Without PF
+// (builds where its four registers per side would spill) the descriptor is
+// loaded when it is needed, as crc64_gather_kernel loads its own.
+template <bool PF>
+struct IovCursor {
+    const photon_crc_iovec* v;
+    uint64_t i, end;           // the current segment and the message's last + 1
+    const uint8_t* p;
+    uint64_t rem;
+    photon_crc_iovec nx[PF ? 1 : 0];
+    __device__ __forceinline__ void take(const photon_crc_iovec& c) {
+        p = static_cast<const uint8_t*>(c.base);
+        rem = c.len;
+        if constexpr (PF) nx[0] = v[i + 1 < end ? i + 1 : i];
+    }
+    __device__ __forceinline__ void begin(const photon_crc_iovec* iov, uint64_t s0, uint64_t s1) {
+        v = iov;
+        i = s0;
+        end = s1;
+        p = nullptr;
+        rem = 0;
+        if constexpr (PF) nx[0] = {nullptr, 0};
+        if (s0 < s1) take(iov[s0]);
+    }
+    __device__ __forceinline__ bool more() const { return i < end; }
+    __device__ __forceinline__ void next() {  // rem == 0: the next segment
+        if (++i < end) {
+            if constexpr (PF) take(nx[0]);
+            else take(v[i]);
+        }
+    }
+};
+
+// One lane group per message, persistent grid and static split as the
+// message kernels. Each step is a piece of n = min(left, src.rem, dst.rem)
+// bytes through the copying unit (copy_begin + buffer_crc<.., COPY>),
+// chained through acc; then the side(s) that ran out take their next
+// segment -- both when the boundaries coincide, neither when the cap ended
+// the message. A zero-length segment on either side makes a zero-length
+// piece: tiny, no loads, no stores, acc unchanged (buf_finish), and only
+// that side advances.
+template <int G, int U>
+__global__ __launch_bounds__(kBlock) void crc32c_copy_iov_kernel(CopyIovArgs args, LaneConsts kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
+    constexpr bool kMsgLead = PCRC_MSG_LEAD != 0;
+    load_tables<G>(lds, kc);
+
+    constexpr int GPW = 64 / G;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = wave_id();
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    const LaneAddr la = lane_addr(lane);
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave; wv * GPW < args.nmsg; wv += nwaves) {
+        const uint64_t m = wv * GPW + grp;
+        const bool active = m < args.nmsg;
+        uint32_t acc = args.seed0;
+        uint64_t left = 0;
+        IovCursor<true> s, d;
+        s.begin(args.src, 0, 0);
+        d.begin(args.dst, 0, 0);
+        if (active) {
+            left = args.size ? args.size[m] : ~0ull;
+            if (args.seeds) acc = args.seeds[m];
+            s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
+            d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
+        }
+        while (left && s.more() && d.more()) {
+            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
+            n = n < left ? n : left;
+            const CopyTo ct = copy_begin<G>(s.p, const_cast<uint8_t*>(d.p), n, gl);
+            acc = buffer_crc<G, U, kMsgLead, true>(lds, s.p, n, acc, gl, la, true, ct);
+            s.p += n;
+            d.p += n;
+            s.rem -= n;
+            d.rem -= n;
+            left -= n;
+            if (!left) break;
+            if (!s.rem) s.next();
+            if (!d.rem) d.next();
+        }
+        if (active && gl == 0) {
+            args.out[m] = acc;
+            // (the cap is read again: two registers less across the walk)
+            if (args.copied) args.copied[m] = (args.size ? args.size[m] : ~0ull) - left;
+        }
+    }
+}
+
 // Per-message fold of per-segment CRCs: acc = seed; acc = acc*x^(8 len)+crc.
 // (Crc32Hasher::extend_hash, rpc/serialize.h:244-252, equals this fold.)
 

@@ -722,6 +722,80 @@ __global__ __launch_bounds__(kBlock) void crc64_gather_kernel(CopyBatch64Args ar
     }
 }
 
+// photon_crc64ecma_copy_msg_iov_n: crc32c_copy_iov_kernel's
+// two-cursor walk (IovCursor, crc32c_kernels.h) with the CRC-64 copying unit.
+// The raw register is chained from piece to piece and broadcast within the
+// group between them, as crc64_gather_kernel does between segments.
+struct CopyIov64Args {
+    const photon_crc_iovec* src;
+    const uint64_t* src_start;
+    const photon_crc_iovec* dst;
+    const uint64_t* dst_start;
+    uint64_t nmsg;
+    const uint64_t* size;      // optional
+    const uint64_t* seeds;     // optional
+    uint64_t* out;
+    uint64_t* copied;          // optional
+    uint64_t seed0;
+};
+
+template <int G>
+__global__ __launch_bounds__(kBlock) void crc64_copy_iov_kernel(CopyIov64Args args, LaneConsts64 kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
+    // Descriptor prefetch within the 128-VGPR budget: both
+    // sides at 64 lanes, the source side alone at 4 and 8, none at 16 and 32
+    // (a descriptor is then loaded when its segment is reached).
+    constexpr bool kPrefetchSrc = G == 64 || G <= 8, kPrefetchDst = G == 64;
+    load_tables64<G>(lds, kc);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    constexpr int GPW = 64 / G;
+    const LaneAddr64 la = lane_addr64(lane);
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave_id(); wv * GPW < args.nmsg; wv += nwaves) {
+        const uint64_t m = wv * GPW + grp;
+        const bool active = m < args.nmsg;
+        uint64_t seed = args.seed0, left = 0;
+        IovCursor<kPrefetchSrc> s;
+        IovCursor<kPrefetchDst> d;
+        s.begin(args.src, 0, 0);
+        d.begin(args.dst, 0, 0);
+        if (active) {
+            left = args.size ? args.size[m] : ~0ull;
+            if (args.seeds) seed = args.seeds[m];
+            s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
+            d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
+        }
+        uint64_t reg = ~seed;  // crc.cpp:119-122
+        while (left && s.more() && d.more()) {
+            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
+            n = n < left ? n : left;
+            const uint8_t* sp = s.p;
+            const CopyTo ct = copy_begin<G>(sp, const_cast<uint8_t*>(d.p), n, gl);
+            // (the cursors move before the rows: the piece's own pointers and
+            // length are then not held across them beside the advanced ones)
+            s.p += n;
+            d.p += n;
+            s.rem -= n;
+            d.rem -= n;
+            left -= n;
+            const uint64_t r = buffer_reg64<G, true>(lds, sp, n, reg, gl, lane, la, true, ct);
+            const uint64_t v = gl == 0 ? r : 0ull;
+            reg = ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+            if (!left) break;
+            if (!s.rem) s.next();
+            if (!d.rem) d.next();
+        }
+        if (active && gl == 0) {
+            args.out[m] = ~reg;
+            // (the cap is read again: two registers less across the walk)
+            if (args.copied) args.copied[m] = (args.size ? args.size[m] : ~0ull) - left;
+        }
+    }
+}
+
 // ------------------------------------------------ full-row uniform batches
 // Strided batches whose buffers are made of whole steps: base and stride
 // 16-byte aligned, nbytes a multiple of 2 * 16 G U (an even number of U-row

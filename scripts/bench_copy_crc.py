@@ -24,6 +24,17 @@ the ratio (b)/(a), and the spread between the alternations of each arm;
                     (photon_crc64ecma_batch_strided after the copy against
                     photon_crc64ecma_copy_batch_strided); adds "margin_over_spread"
                     = ((a) - (b)) / the larger spread and "faster_3x" (margin > 3)
+  --iov : copy + CRC between iovectors (photon_crc32c_copy_msg_iov_n; with
+                    --crc64 photon_crc64ecma_copy_msg_iov_n), the same method, three
+                    arms over 8,192 messages of 8 co-aligned 8 KiB source segments:
+                    "gather" = photon_crc32c_gather_msg_n into one 64 KiB run per
+                    message; "iov" = the new call into ONE 64 KiB destination
+                    segment per message (the same loads and stores); "reseg" = the
+                    new call into 16 destination segments of 4 KiB per message
+                    (no equal-work baseline). "within" is true when |iov - gather|
+                    is at most the larger of 3 % of gather and three times the
+                    spread between gather's alternations. --out appends here, so
+                    the CRC-32C and the CRC-64 run share one file.
 """
 import argparse
 import csv
@@ -44,6 +55,7 @@ ap.add_argument("--out", help="also write the JSON lines to this file")
 ap.add_argument("--pmc-run")
 ap.add_argument("--pmc-summary")
 ap.add_argument("--crc64", action="store_true")
+ap.add_argument("--iov", action="store_true")
 args = ap.parse_args()
 
 
@@ -150,6 +162,95 @@ def bench(shape):
         res["faster_3x"] = bool(res["margin_over_spread"] > 3)
     return res
 
+
+def bench_iov():
+    nmsg, nseg_m, seg, blk = 8192, 8, 8192, 4096
+    nseg, msg = nmsg * nseg_m, nseg_m * seg
+    nblk = nmsg * msg // blk
+    total = nmsg * msg
+    src = torch.empty(total, dtype=torch.uint8, device="cuda")
+    dst = torch.zeros(total, dtype=torch.uint8, device="cuda")
+    ck.fill_splitmix(src, seg, seg, nseg, 0x5EED0101)
+    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).cuda()
+    # segment s of the stream of messages sits in source slot (4099 s) mod nseg: a scatter-gather list
+    slot = (np.arange(nseg, dtype=np.uint64) * np.uint64(4099)) % np.uint64(nseg)
+    siov = np.empty((nseg, 2), np.uint64)
+    siov[:, 0] = np.uint64(src.data_ptr()) + slot * np.uint64(seg)
+    siov[:, 1] = seg
+    # "iov": one destination segment per message; "reseg": block q of the stream in slot (8191 q) mod nblk
+    d1 = np.empty((nmsg, 2), np.uint64)
+    d1[:, 0] = np.uint64(dst.data_ptr()) + np.arange(nmsg, dtype=np.uint64) * np.uint64(msg)
+    d1[:, 1] = msg
+    bslot = (np.arange(nblk, dtype=np.uint64) * np.uint64(8191)) % np.uint64(nblk)
+    d16 = np.empty((nblk, 2), np.uint64)
+    d16[:, 0] = np.uint64(dst.data_ptr()) + bslot * np.uint64(blk)
+    d16[:, 1] = blk
+    d_siov, d_sstart = i64(siov), i64(np.arange(nmsg + 1, dtype=np.uint64) * np.uint64(nseg_m))
+    d_d1, d_d1start = i64(d1), i64(np.arange(nmsg + 1, dtype=np.uint64))
+    d_d16, d_d16start = i64(d16), i64(np.arange(nmsg + 1, dtype=np.uint64) * np.uint64(msg // blk))
+    d_ptrs = i64(d1[:, 0])
+    out = torch.zeros(nmsg, dtype=torch.int64 if args.crc64 else torch.int32, device="cuda")
+    gather = ck.gather64_msg_n if args.crc64 else ck.gather_msg_n
+    copy_iov = ck.copy_msg64_iov_n if args.crc64 else ck.copy_msg_iov_n
+    arms = {
+        "gather": lambda: gather(d_siov, d_sstart, nmsg, nseg, d_ptrs, None, out, stream=st),
+        "iov": lambda: copy_iov(d_siov, d_sstart, nseg, d_d1, d_d1start, nmsg, nmsg, out, stream=st),
+        "reseg": lambda: copy_iov(d_siov, d_sstart, nseg, d_d16, d_d16start, nblk, nmsg, out, stream=st),
+    }
+    stream_bytes = src.view(nseg, seg)[torch.from_numpy(slot.astype(np.int64)).cuda()].reshape(-1)
+    crcs = {}
+    for name, fn in arms.items():  # same CRCs, the right bytes landed, before anything is timed
+        dst.zero_()
+        out.zero_()
+        fn()
+        torch.cuda.synchronize()
+        landed = dst if name != "reseg" else dst.view(nblk, blk)[torch.from_numpy(bslot.astype(np.int64)).cuda()].reshape(-1)
+        assert torch.equal(landed, stream_bytes), f"{name}: destination differs from the source stream"
+        crcs[name] = out.cpu().numpy().copy()
+    assert np.array_equal(crcs["gather"], crcs["iov"]) and np.array_equal(crcs["gather"], crcs["reseg"]), \
+        "the arms' CRCs differ"
+    del stream_bytes
+    means = {k: [] for k in arms}
+    times = {k: [] for k in arms}
+    for r in range(args.rounds):
+        for name in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+            fn = arms[name]
+            for _ in range(args.warmup):
+                fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.reps + 1)]
+            ev[0].record(st)
+            for k in range(args.reps):
+                fn()
+                ev[k + 1].record(st)
+            torch.cuda.synchronize()
+            t = [ev[k].elapsed_time(ev[k + 1]) for k in range(args.reps)]
+            times[name] += t
+            means[name].append(float(np.mean(t)))
+    gib = total / 2.0**30
+    res = {"shape": "iov", "crc": "crc64ecma" if args.crc64 else "crc32c", "nmsg": nmsg, "src_segments": nseg_m,
+           "src_segment_bytes": seg, "reseg_block_bytes": blk, "rounds": args.rounds, "reps": args.reps,
+           "warmup": args.warmup}
+    for name in arms:
+        ms = np.asarray(times[name])
+        res[name] = {"ms_mean": round(float(ms.mean()), 5), "ms_median": round(float(np.median(ms)), 5),
+                     "payload_GiBps_mean": round(gib / (ms.mean() * 1e-3), 1),
+                     "round_means_ms": [round(m, 5) for m in means[name]],
+                     "spread_ms": round(max(means[name]) - min(means[name]), 5)}
+    a, b = res["gather"]["ms_mean"], res["iov"]["ms_mean"]
+    res["ratio_iov_over_gather"] = round(b / a, 4)
+    res["ratio_reseg_over_gather"] = round(res["reseg"]["ms_mean"] / a, 4)
+    res["allowed_ms"] = round(max(0.03 * a, 3 * res["gather"]["spread_ms"]), 5)
+    res["within"] = bool(abs(b - a) <= res["allowed_ms"])
+    return res
+
+
+if args.iov:
+    line = json.dumps(bench_iov())
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    sys.exit(0)
 
 lines = []
 for shape in ([args.pmc_run] if args.pmc_run else args.shapes.split(",")):
