@@ -194,13 +194,39 @@ int photon_crc32c_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_
  * destination segments may sit back to back at odd addresses. The alignment
  * rule holds per piece (a run of bytes inside one source and one destination
  * segment): a piece with (dst - src) % 16 == 0 is read once, any other is
- * copied first and checksummed from the cache. No per-segment CRCs: a piece
- * is in general neither a source nor a destination segment. */
+ * copied first and checksummed from the cache. No per-segment CRCs here (a
+ * piece is in general neither a source nor a destination segment); for one
+ * CRC per segment of ONE side see photon_crc32c_copy_msg_iov_seg_n below. */
 int photon_crc32c_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
                                  const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
                                  uint64_t nmsg, const uint64_t* d_size,
                                  uint32_t seed0, const uint32_t* d_seeds,
                                  uint32_t* d_out, uint64_t* d_copied, void* stream);
+
+/* photon_crc32c_copy_msg_iov_n that also returns one CRC per segment of one
+ * side, from the same read. The copy, k_m, d_out[m] (bit-identical) and
+ * d_copied[m] are those of the call above, and so are the alignment rule and
+ * contract (iv). seg_side chooses the side: PHOTON_CRC_SEG_OF_SRC (d_seg_out
+ * has nsrc entries, indexed like d_src: the read direction, blocks that carry
+ * a stored CRC each assembled into a caller's iovector) or
+ * PHOTON_CRC_SEG_OF_DST (ndst entries, indexed like d_dst: the write
+ * direction, a payload scattered into blocks that are stored with a CRC each).
+ * d_seg_out[s] = crc32c_extend from seed 0 over the bytes of segment s that
+ * took part in the copy: the whole segment where the copy covered it, the
+ * copied prefix for the segment in which the copy ended, 0 (the CRC of no
+ * bytes) for a zero-length segment and for every segment behind the end of
+ * the copy. Every entry of all nmsg messages is written, none beyond them.
+ * d_out[m] equals the fold acc = seed_m; acc = crc32c_combine(acc,
+ * d_seg_out[s], landed length of s) over message m's segments of that side.
+ * A null d_seg_out, or a seg_side other than the two above, gives -EINVAL. */
+#define PHOTON_CRC_SEG_OF_SRC 0
+#define PHOTON_CRC_SEG_OF_DST 1
+int photon_crc32c_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                     const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                     uint64_t nmsg, const uint64_t* d_size,
+                                     uint32_t seed0, const uint32_t* d_seeds,
+                                     int seg_side, uint32_t* d_seg_out,
+                                     uint32_t* d_out, uint64_t* d_copied, void* stream);
 
 /* d_out[i] = crc32c_combine(d_crc1[i], d_crc2[i], d_len2[i]) with the
  * reference's shortcuts (crc1 == 0 -> crc2, len2 == 0 -> crc1). */
@@ -367,6 +393,15 @@ int photon_crc64ecma_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_
                                     uint64_t nmsg, const uint64_t* d_size,
                                     uint64_t seed0, const uint64_t* d_seeds,
                                     uint64_t* d_out, uint64_t* d_copied, void* stream);
+/* photon_crc32c_copy_msg_iov_seg_n for CRC-64/ECMA: the same arguments and
+ * contract; d_seg_out[s] = crc64ecma_extend from seed 0 over the bytes of
+ * segment s that took part in the copy. */
+int photon_crc64ecma_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                        const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                        uint64_t nmsg, const uint64_t* d_size,
+                                        uint64_t seed0, const uint64_t* d_seeds,
+                                        int seg_side, uint64_t* d_seg_out,
+                                        uint64_t* d_out, uint64_t* d_copied, void* stream);
 /* photon_crc32c_extend_device for CRC-64/ECMA (crc64ecma_extend, crc.cpp:
  * 119-122): the same latency path for spans up to 256 KiB (a small kernel of
  * up to 33 workgroups), one launch over the chip above, the same per-stream

@@ -31,6 +31,7 @@ __all__ = [
     "crc64ecma_combine_series", "crc64ecma_trim",
     "copy_batch64_strided", "copy_batch64_iov", "gather64_msg_n",
     "copy_msg_iov_n", "copy_msg64_iov_n",
+    "copy_msg_iov_seg_n", "copy_msg64_iov_seg_n", "SEG_OF_SRC", "SEG_OF_DST",
     "batch64_strided", "batch64_iov", "combine64_batch", "trim64_batch", "batch64_msg_n", "host_batch64_strided", "extend64_device", "extend_spans", "extend64_spans", "Span", "combine_batch", "fill_splitmix", "read_stream", "IOVEC_DTYPE",
 ]
 
@@ -436,6 +437,31 @@ def copy_msg64_iov_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nmsg, o
     _check(lib().photon_crc64ecma_copy_msg_iov_n(_ptr(src_iov), _ptr(src_start), nsrc, _ptr(dst_iov),
                                                  _ptr(dst_start), ndst, nmsg, _ptr(size), seed & 0xFFFFFFFFFFFFFFFF,
                                                  _ptr(seeds), _ptr(out), _ptr(copied), _stream(stream)))
+
+
+SEG_OF_SRC, SEG_OF_DST = 0, 1  # PHOTON_CRC_SEG_OF_SRC / PHOTON_CRC_SEG_OF_DST
+
+
+def copy_msg_iov_seg_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nmsg, seg_side, seg_out, out, size=None,
+                       seed=0, seeds=None, copied=None, stream=None):
+    """copy_msg_iov_n that also returns one CRC-32C per segment of one side:
+    seg_out has nsrc entries for seg_side = SEG_OF_SRC (0), ndst for SEG_OF_DST
+    (1), indexed like that side's descriptors; seg_out[s] = crc32c_extend from
+    seed 0 over the bytes of segment s that were copied (0 behind the end of
+    the copy), every entry written. out / copied as copy_msg_iov_n. Async."""
+    _check(lib().photon_crc32c_copy_msg_iov_seg_n(_ptr(src_iov), _ptr(src_start), nsrc, _ptr(dst_iov),
+                                                  _ptr(dst_start), ndst, nmsg, _ptr(size), seed & 0xFFFFFFFF,
+                                                  _ptr(seeds), seg_side, _ptr(seg_out), _ptr(out), _ptr(copied),
+                                                  _stream(stream)))
+
+
+def copy_msg64_iov_seg_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nmsg, seg_side, seg_out, out, size=None,
+                         seed=0, seeds=None, copied=None, stream=None):
+    """copy_msg_iov_seg_n for CRC-64/ECMA (uint64 seeds / seg_out / out). Async."""
+    _check(lib().photon_crc64ecma_copy_msg_iov_seg_n(_ptr(src_iov), _ptr(src_start), nsrc, _ptr(dst_iov),
+                                                     _ptr(dst_start), ndst, nmsg, _ptr(size),
+                                                     seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), seg_side, _ptr(seg_out),
+                                                     _ptr(out), _ptr(copied), _stream(stream)))
 
 
 def extend64_device(data, nbytes, out, seed=0, stream=None):

@@ -566,6 +566,42 @@ int launch_copy_iov(const CopyIovArgs& a, int g, hipStream_t stream) {
     return 0;
 }
 
+// crc32c_copy_iov_seg_kernel<G, U, DST>: as launch_copy_iov,
+// one build per lane-group size and side.
+int launch_copy_iov_seg(const CopyIovSegArgs& a, bool dst_side, int g, hipStream_t stream) {
+    if (a.nmsg == 0) return 0;
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint64_t gpw = 64 / g;
+    const uint64_t waves = (a.nmsg + gpw - 1) / gpw;
+    uint64_t grid = (waves + kWaves - 1) / kWaves;
+    if (grid > (uint64_t)cus) grid = cus;
+    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
+    const LaneConsts& kc = lane_consts(g);
+    HeavyLaunch heavy(stream);
+#define LCS(GG, UU)                                                                                                  \
+    do {                                                                                                             \
+        if (dst_side)                                                                                                \
+            hipLaunchKernelGGL((crc32c_copy_iov_seg_kernel<GG, UU, true>), dim3(grid), dim3(kBlock), 0, stream, a,   \
+                               kc, pow_table());                                                                     \
+        else                                                                                                         \
+            hipLaunchKernelGGL((crc32c_copy_iov_seg_kernel<GG, UU, false>), dim3(grid), dim3(kBlock), 0, stream, a,  \
+                               kc, pow_table());                                                                     \
+    } while (0)
+    switch (g) {
+        case 64: LCS(64, 4); break;
+        case 32: LCS(32, 4); break;
+        case 16: LCS(16, 2); break;
+        case 8: LCS(8, 4); break;
+        default: LCS(4, 4); break;
+    }
+#undef LCS
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "crc32c_copy_iov_seg_kernel launch");
+    return 0;
+}
+
 LaneConsts64 make_lane_consts64(int g) {
     LaneConsts64 c;
     c.kshift = xpow64(8ull * 16ull * (uint64_t)g);
@@ -718,6 +754,50 @@ int launch_copy_iov64(const CopyIov64Args& a, int g, hipStream_t stream) {
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "crc64_copy_iov_kernel launch");
+    return 0;
+#endif
+}
+
+// crc64_copy_iov_seg_kernel<G, DST> and the fold of its segment CRCs
+// (DESIGN.md §4.6), both on `stream`: the grid as launch_copy_iov64.
+int launch_copy_iov_seg64(const CopyIovSeg64Args& a, bool dst_side, uint64_t seed0, const uint64_t* d_seeds,
+                          uint64_t* d_out, int g, hipStream_t stream) {
+    if (a.nmsg == 0) return 0;
+#if PCRC64_ABL != 0 || PCRC64_ROLL != 1 || PCRC64_U != 2
+    return fail(-ENOTSUP, "the copying CRC-64 kernels are not part of this A/B build");
+#else
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint64_t gpw = 64 / g;
+    const uint64_t waves = (a.nmsg + gpw - 1) / gpw;
+    uint64_t grid = (waves + kWaves - 1) / kWaves;
+    if (grid > (uint64_t)cus) grid = cus;
+    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
+    const LaneConsts64& kc = lane_consts64(g);
+    HeavyLaunch heavy(stream);
+#define LCS64(GG)                                                                                                    \
+    do {                                                                                                             \
+        if (dst_side)                                                                                                \
+            hipLaunchKernelGGL((crc64_copy_iov_seg_kernel<GG, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc);   \
+        else                                                                                                         \
+            hipLaunchKernelGGL((crc64_copy_iov_seg_kernel<GG, false>), dim3(grid), dim3(kBlock), 0, stream, a, kc);  \
+    } while (0)
+    switch (g) {
+        case 64: LCS64(64); break;
+        case 32: LCS64(32); break;
+        case 16: LCS64(16); break;
+        case 8: LCS64(8); break;
+        default: LCS64(4); break;
+    }
+#undef LCS64
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "crc64_copy_iov_seg_kernel launch");
+    hipLaunchKernelGGL(crc64_seg_fold_kernel, dim3((a.nmsg + kSegFoldBlock / 64 - 1) / (kSegFoldBlock / 64)),
+                       dim3(kSegFoldBlock), 0, stream, a, dst_side ? 1 : 0,
+                       seed0, d_seeds, d_out, pow_table64());
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "crc64_seg_fold_kernel launch");
     return 0;
 #endif
 }
@@ -1762,6 +1842,32 @@ int photon_crc32c_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_t* 
     return launch_copy_iov(a, choose_lanes(8192), static_cast<hipStream_t>(stream));
 }
 
+int photon_crc32c_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                     const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                     uint64_t nmsg, const uint64_t* d_size, uint32_t seed0, const uint32_t* d_seeds,
+                                     int seg_side, uint32_t* d_seg_out, uint32_t* d_out, uint64_t* d_copied,
+                                     void* stream) {
+    if (!nmsg) return 0;
+    if (!d_src_start || !d_dst_start || !d_out || !d_seg_out || (!d_src && nsrc) || (!d_dst && ndst))
+        return fail(-EINVAL, "null argument");
+    if (seg_side != PHOTON_CRC_SEG_OF_SRC && seg_side != PHOTON_CRC_SEG_OF_DST)
+        return fail(-EINVAL, "seg_side is neither PHOTON_CRC_SEG_OF_SRC nor PHOTON_CRC_SEG_OF_DST");
+    CopyIovSegArgs a{};
+    a.src = d_src;
+    a.src_start = d_src_start;
+    a.dst = d_dst;
+    a.dst_start = d_dst_start;
+    a.nmsg = nmsg;
+    a.size = d_size;
+    a.seeds = d_seeds;
+    a.seg_out = d_seg_out;
+    a.out = d_out;
+    a.copied = d_copied;
+    a.seed0 = seed0;
+    return launch_copy_iov_seg(a, seg_side == PHOTON_CRC_SEG_OF_DST, choose_lanes(8192),
+                               static_cast<hipStream_t>(stream));
+}
+
 int photon_crc64ecma_batch_strided(const void* d_base, uint64_t stride, uint64_t nbytes, uint64_t count,
                                    uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out, void* stream) {
     if (count && (!d_out || (!d_base && nbytes))) return fail(-EINVAL, "null buffer or output");
@@ -1938,6 +2044,29 @@ int photon_crc64ecma_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_
     a.copied = d_copied;
     a.seed0 = seed0;
     return launch_copy_iov64(a, choose_lanes(8192), static_cast<hipStream_t>(stream));
+}
+
+int photon_crc64ecma_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                        const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                        uint64_t nmsg, const uint64_t* d_size, uint64_t seed0,
+                                        const uint64_t* d_seeds, int seg_side, uint64_t* d_seg_out, uint64_t* d_out,
+                                        uint64_t* d_copied, void* stream) {
+    if (!nmsg) return 0;
+    if (!d_src_start || !d_dst_start || !d_out || !d_seg_out || (!d_src && nsrc) || (!d_dst && ndst))
+        return fail(-EINVAL, "null argument");
+    if (seg_side != PHOTON_CRC_SEG_OF_SRC && seg_side != PHOTON_CRC_SEG_OF_DST)
+        return fail(-EINVAL, "seg_side is neither PHOTON_CRC_SEG_OF_SRC nor PHOTON_CRC_SEG_OF_DST");
+    CopyIovSeg64Args a{};
+    a.src = d_src;
+    a.src_start = d_src_start;
+    a.dst = d_dst;
+    a.dst_start = d_dst_start;
+    a.nmsg = nmsg;
+    a.size = d_size;
+    a.seg_out = d_seg_out;
+    a.copied = d_copied;
+    return launch_copy_iov_seg64(a, seg_side == PHOTON_CRC_SEG_OF_DST, seed0, d_seeds, d_out, choose_lanes(8192),
+                                 static_cast<hipStream_t>(stream));
 }
 
 int photon_crc64ecma_extend_device(const void* d_data, uint64_t nbytes, uint64_t seed, uint64_t* d_out,

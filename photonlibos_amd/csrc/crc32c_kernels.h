@@ -1381,6 +1381,153 @@ __global__ __launch_bounds__(kBlock) void crc32c_copy_iov_kernel(CopyIovArgs arg
     }
 }
 
+// photon_crc32c_copy_msg_iov_seg_n: the walk above, with one
+// CRC per segment of ONE side (the source's or the destination's) beside the
+// message CRC.
+struct CopyIovSegArgs {
+    const photon_crc_iovec* src;
+    const uint64_t* src_start;
+    const photon_crc_iovec* dst;
+    const uint64_t* dst_start;
+    uint64_t nmsg;
+    const uint64_t* size;      // optional
+    const uint32_t* seeds;     // optional
+    uint32_t* seg_out;         // one entry per descriptor of the chosen side
+    uint32_t* out;
+    uint64_t* copied;          // optional
+    uint32_t seed0;
+};
+
+// acc * x^(8 n) ^ c for the walk below: the lane-spread multiply of
+// crc32c_batch_kernel<G, U, 2> with its length-keyed basis cache (lane gl
+// holds the images under K = x^(8n) of the register bits gl*W .. gl*W+W-1,
+// rebuilt only when n changes; 4-lane groups multiply on every lane).
+template <int G>
+struct SegFold {
+    static constexpr int W = G >= 32 ? 1 : G >= 8 ? 32 / G : 1;
+    uint64_t klen;
+    uint32_t kb[W];
+    __device__ __forceinline__ void init() {
+        klen = ~0ull;
+#pragma unroll
+        for (int w = 0; w < W; ++w) kb[w] = 0;
+    }
+    __device__ __forceinline__ uint32_t apply(uint32_t acc, uint32_t c, uint64_t n, uint32_t gl, const PowTable& pt) {
+        if constexpr (G >= 8) {
+            if (n != klen) {
+                uint32_t r = kOne;
+                uint64_t m = n;
+#pragma unroll 1
+                for (int i = 0; m; ++i, m >>= 1)
+                    if (m & 1) r = mulmod_rolled(r, pt.x8pow2[i]);
+#pragma unroll
+                for (int w = 0; w < W; ++w) kb[w] = 0u;
+#pragma unroll 1
+                for (uint32_t j = 0; j < 32; ++j) {  // r = K * x^j, bit 31 - j
+#pragma unroll
+                    for (int w = 0; w < W; ++w) kb[w] = gl * W + w == 31u - j ? r : kb[w];
+                    r = (r >> 1) ^ ((0u - (r & 1u)) & kPoly);
+                }
+                klen = n;
+            }
+            uint32_t part = 0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                const uint32_t bit = gl * W + w;  // >= 32 only for 64-lane groups (kb[w] = 0 there)
+                part ^= (bit < 32 && ((acc >> (bit & 31u)) & 1u)) ? kb[w] : 0u;
+            }
+            return group_xor<G>(part) ^ c;  // acc and c are valid on every lane of the group
+        } else {
+            if (n != klen) {
+                kb[0] = xpow8_tab(n, pt);
+                klen = n;
+            }
+            return mulmod(acc, kb[0]) ^ c;
+        }
+    }
+};
+
+// DST: the chosen side. The piece loop is crc32c_copy_iov_kernel's; the
+// running value `sc` is chained through the seed from piece to piece within
+// a chosen-side segment and starts from 0 when that side's cursor takes a new
+// segment. When the cursor's rem reaches 0 the segment's CRC is final: the
+// group's first lane stores it at once (as the copying form of
+// crc32c_batch_kernel<G, U, 2, true> stores its own), and it is folded into
+// the message accumulator with K = x^(8 * landed length), there and then
+// (holding the fold back until the next piece's first loads are issued, as
+// the message kernel does, took three more registers: the 8-lane build
+// spilled). The piece loop gains no multiply. The segment in which the walk
+// ended (cap reached, the other side exhausted, or nothing copied at all)
+// gets the CRC of its landed prefix after the walk, and the entries behind it
+// are zeroed by the group: only the index range [cursor.i + 1, end) is needed.
+template <int G, int U, bool DST>
+__global__ __launch_bounds__(kBlock) void crc32c_copy_iov_seg_kernel(CopyIovSegArgs args, LaneConsts kc, PowTable pt) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
+    constexpr bool kMsgLead = PCRC_MSG_LEAD != 0;
+    load_tables<G>(lds, kc);
+
+    constexpr int GPW = 64 / G;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = wave_id();
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    const LaneAddr la = lane_addr(lane);
+    SegFold<G> fold;
+    fold.init();
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave; wv * GPW < args.nmsg; wv += nwaves) {
+        const uint64_t m = wv * GPW + grp;
+        const bool active = m < args.nmsg;
+        uint32_t acc = args.seed0;
+        uint64_t left = 0;
+        IovCursor<true> s, d;
+        s.begin(args.src, 0, 0);
+        d.begin(args.dst, 0, 0);
+        if (active) {
+            left = args.size ? args.size[m] : ~0ull;
+            if (args.seeds) acc = args.seeds[m];
+            s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
+            d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
+        }
+        IovCursor<true>& c = DST ? d : s;  // the chosen side
+        uint32_t sc = 0;       // the current chosen-side segment's CRC so far
+        uint64_t sl = 0;       // and how many of its bytes have landed
+        while (left && s.more() && d.more()) {
+            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
+            n = n < left ? n : left;
+            const CopyTo ct = copy_begin<G>(s.p, const_cast<uint8_t*>(d.p), n, gl);
+            sc = buffer_crc<G, U, kMsgLead, true>(lds, s.p, n, sc, gl, la, true, ct);
+            s.p += n;
+            d.p += n;
+            s.rem -= n;
+            d.rem -= n;
+            left -= n;
+            sl += n;
+            if (!left) break;
+            if (!c.rem) {  // the chosen side's segment is complete (an empty one: 0, nothing to fold)
+                if (gl == 0) args.seg_out[c.i] = sc;
+                if (sl) acc = fold.apply(acc, sc, sl, gl, pt);
+                sc = 0;
+                sl = 0;
+            }
+            if (!s.rem) s.next();
+            if (!d.rem) d.next();
+        }
+        if (c.more()) {
+            // The walk ended in segment c.i (or before its first byte): its
+            // landed prefix, then 0 = the CRC of no bytes for the rest.
+            if (gl == 0) args.seg_out[c.i] = sc;
+            if (sl) acc = fold.apply(acc, sc, sl, gl, pt);
+            for (uint64_t k = c.i + 1 + gl; k < c.end; k += G) args.seg_out[k] = 0u;
+        }
+        if (active && gl == 0) {
+            args.out[m] = acc;
+            if (args.copied) args.copied[m] = (args.size ? args.size[m] : ~0ull) - left;
+        }
+    }
+}
+
 // Per-message fold of per-segment CRCs: acc = seed; acc = acc*x^(8 len)+crc.
 // (Crc32Hasher::extend_hash, rpc/serialize.h:244-252, equals this fold.)
 

@@ -796,6 +796,86 @@ __global__ __launch_bounds__(kBlock) void crc64_copy_iov_kernel(CopyIov64Args ar
     }
 }
 
+// photon_crc64ecma_copy_msg_iov_seg_n: the walk above with
+// one CRC per segment of ONE side (DST: the destination's, else the
+// source's). Two kernels, as crc64_gather_kernel with seg_out: this one
+// chains the raw register within a chosen-side segment, starts it from ~0
+// when that side's cursor takes a new segment, and stores the segment's CRC
+// at once when the cursor's rem reaches 0 or the walk ends.
+// crc64_seg_fold_kernel then folds them into out[] with the LANDED lengths,
+// writes copied[] and zeroes the entries of the segments of which no byte
+// landed (those behind the end of the copy among them): neither the message
+// seed nor m is needed here after the walk has begun, and with the zeroing
+// loop in this kernel the 4- to 32-lane builds spilled 3 to 8 registers.
+struct CopyIovSeg64Args {
+    const photon_crc_iovec* src;
+    const uint64_t* src_start;
+    const photon_crc_iovec* dst;
+    const uint64_t* dst_start;
+    uint64_t nmsg;
+    const uint64_t* size;      // optional
+    uint64_t* seg_out;         // one entry per descriptor of the chosen side
+    uint64_t* copied;          // optional
+};
+
+template <int G, bool DST>
+__global__ __launch_bounds__(kBlock) void crc64_copy_iov_seg_kernel(CopyIovSeg64Args args, LaneConsts64 kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
+    // Descriptor prefetch as crc64_copy_iov_kernel (the 128-VGPR budget).
+    constexpr bool kPrefetchSrc = G == 64 || G <= 8, kPrefetchDst = G == 64;
+    load_tables64<G>(lds, kc);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    constexpr int GPW = 64 / G;
+    const LaneAddr64 la = lane_addr64(lane);
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave_id(); wv * GPW < args.nmsg; wv += nwaves) {
+        const uint64_t m = wv * GPW + grp;
+        const bool active = m < args.nmsg;
+        uint64_t left = 0;
+        IovCursor<kPrefetchSrc> s;
+        IovCursor<kPrefetchDst> d;
+        s.begin(args.src, 0, 0);
+        d.begin(args.dst, 0, 0);
+        if (active) {
+            left = args.size ? args.size[m] : ~0ull;
+            s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
+            d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
+        }
+        uint64_t reg = ~0ull;  // the current chosen-side segment's register (seed 0; crc.cpp:119-122)
+        while (left && s.more() && d.more()) {
+            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
+            n = n < left ? n : left;
+            const uint8_t* sp = s.p;
+            const CopyTo ct = copy_begin<G>(sp, const_cast<uint8_t*>(d.p), n, gl);
+            s.p += n;
+            d.p += n;
+            s.rem -= n;
+            d.rem -= n;
+            left -= n;
+            const uint64_t r = buffer_reg64<G, true>(lds, sp, n, reg, gl, lane, la, true, ct);
+            const uint64_t v = gl == 0 ? r : 0ull;
+            reg = ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+            if (!left) break;
+            if (!(DST ? d.rem : s.rem)) {  // the chosen side's segment is complete
+                if (gl == 0) args.seg_out[DST ? d.i : s.i] = ~reg;
+                reg = ~0ull;
+            }
+            if (!s.rem) s.next();
+            if (!d.rem) d.next();
+        }
+        const uint64_t ci = DST ? d.i : s.i, cend = DST ? d.end : s.end;
+        if (ci < cend) {
+            // The walk ended in segment ci (or before its first byte): its
+            // landed prefix (the rest: crc64_seg_fold_kernel).
+            if (gl == 0) args.seg_out[ci] = ~reg;
+        }
+        // (copied[m] is written by crc64_seg_fold_kernel, which has k_m)
+    }
+}
+
 // ------------------------------------------------ full-row uniform batches
 // Strided batches whose buffers are made of whole steps: base and stride
 // 16-byte aligned, nbytes a multiple of 2 * 16 G U (an even number of U-row
@@ -978,6 +1058,87 @@ __global__ void crc64_msg_fold_kernel(const photon_crc_iovec* iov, const uint64_
             }
     }
     out[m] = acc;
+}
+
+// The fold of crc64_copy_iov_seg_kernel's segment CRCs, one
+// WAVEFRONT per message (one thread per message, as crc64_msg_fold_kernel,
+// is a chain of 40 dependent loads and 16 64-step multiplies per thread for
+// a message of 16 blocks). A segment counts with the bytes of
+// it that LANDED, not with its descriptor length: k_m = min(size_m, sum src,
+// sum dst) is recomputed from the descriptors (the lanes stride over them;
+// saturating sums; no payload is read) and consumed along the chosen side's
+// segments, 64 descriptors and segment CRCs loaded at a time. acc * x^(8n) is
+// spread over the wave: lane b holds the image of register bit b under
+// K = x^(8n) (rebuilt when n changes: once per message of equal blocks, by
+// 64 single x-steps from K), so a segment costs a select and an XOR reduction. A segment of which nothing
+// landed gets its 0 here (the walk stored the others), and copied[m] = k_m.
+constexpr int kSegFoldBlock = 256;
+
+__device__ __forceinline__ uint64_t wave_bcast64(uint64_t v, uint32_t j) {  // j: wave-uniform
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)j) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)j);
+}
+
+__global__ __launch_bounds__(kSegFoldBlock) void crc64_seg_fold_kernel(CopyIovSeg64Args a, int dst_side,
+                                                                       uint64_t seed0, const uint64_t* seeds,
+                                                                       uint64_t* out, PowTable64 pt) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t m = (uint64_t)blockIdx.x * (kSegFoldBlock / 64) + wave_id();
+    if (m >= a.nmsg) return;  // wave-uniform
+    auto total = [&](const photon_crc_iovec* v, uint64_t s0, uint64_t s1) {
+        uint64_t t = 0;
+        for (uint64_t s = s0 + lane; s < s1; s += 64) {
+            const uint64_t n = v[s].len;
+            t = t + n < t ? ~0ull : t + n;
+        }
+        for (int off = 32; off; off >>= 1) {
+            const uint64_t o = ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(t >> 32), off, 64) << 32) |
+                               (uint32_t)__shfl_xor((int)(uint32_t)t, off, 64);
+            t = t + o < t ? ~0ull : t + o;
+        }
+        return t;  // on every lane
+    };
+    const uint64_t ssum = total(a.src, a.src_start[m], a.src_start[m + 1]);
+    const uint64_t dsum = total(a.dst, a.dst_start[m], a.dst_start[m + 1]);
+    uint64_t rem = a.size ? a.size[m] : ~0ull;
+    rem = rem < ssum ? rem : ssum;
+    rem = rem < dsum ? rem : dsum;
+    if (a.copied && lane == 0) a.copied[m] = rem;
+    const photon_crc_iovec* v = dst_side ? a.dst : a.src;
+    const uint64_t* start = dst_side ? a.dst_start : a.src_start;
+    const uint64_t s0 = start[m], s1 = start[m + 1];
+    uint64_t acc = seeds ? seeds[m] : seed0;
+    uint64_t klen = 0, kb = 1ull << lane;  // K = 1: bit b's image is itself
+    for (uint64_t base = s0; base < s1; base += 64) {
+        const uint64_t s = base + lane;
+        const uint64_t len = s < s1 ? v[s].len : 0ull;
+        const uint64_t crc = s < s1 ? a.seg_out[s] : 0ull;  // (not yet known to have landed: in bounds anyway)
+        const uint32_t cnt = s1 - base < 64 ? (uint32_t)(s1 - base) : 64u;
+        for (uint32_t j = 0; j < cnt; ++j) {  // everything below is wave-uniform but `lane`
+            uint64_t n = wave_bcast64(len, j);
+            n = n < rem ? n : rem;
+            rem -= n;
+            if (!n) {  // empty, or behind the end of the copy: the CRC of no bytes
+                if (lane == 0) a.seg_out[base + j] = 0ull;
+                continue;
+            }
+            if (n != klen) {
+                // lane b: K * x^(63 - b), by single x-steps from K (a 64-step
+                // multiply per lane instead: half of this kernel's time)
+                uint64_t r = xpow8_tab64(n, pt);
+#pragma unroll 1
+                for (uint32_t i = 0; i < 64; ++i) {  // r = K * x^i, bit 63 - i
+                    kb = lane == 63u - i ? r : kb;
+                    r = (r >> 1) ^ ((0ull - (r & 1ull)) & kPoly64);
+                }
+                klen = n;
+            }
+            const uint64_t part = (acc >> lane) & 1ull ? kb : 0ull;
+            acc = (((uint64_t)group_xor<64>((uint32_t)(part >> 32)) << 32) | group_xor<64>((uint32_t)part)) ^
+                  wave_bcast64(crc, j);
+        }
+    }
+    if (lane == 0) out[m] = acc;
 }
 
 // photon_crc64ecma_extend_device in one launch: crc32c_long_kernel's scheme

@@ -35,6 +35,20 @@ the ratio (b)/(a), and the spread between the alternations of each arm;
                     is at most the larger of 3 % of gather and three times the
                     spread between gather's alternations. --out appends here, so
                     the CRC-32C and the CRC-64 run share one file.
+  --iov-seg : per-segment CRCs from the copy between iovectors
+                    (photon_crc32c_copy_msg_iov_seg_n; with --crc64 the CRC-64 call), the
+                    same method over the "reseg" shape of --iov: 8,192 messages of 8
+                    co-aligned 8 KiB source segments in permuted slots into 16 blocks
+                    of 4 KiB in permuted slots. "plain" = copy_msg_iov_n alone (no
+                    segment CRCs: the floor); "pair" = what a caller did before:
+                    copy_msg_iov_n, then batch_iov over the 131,072 destination blocks
+                    on the same stream (3 bytes moved per payload byte); "seg_dst" =
+                    the new call, a CRC per destination block (2 bytes per payload
+                    byte; floor for seg_dst/pair ~ 0.67); "plain_mirror" / "seg_src" =
+                    the mirrored shape (16 blocks of 4 KiB into 8 segments of 8 KiB)
+                    through copy_msg_iov_n and through the new call with a CRC per
+                    source block. "faster_3x" is true when pair - seg_dst exceeds three
+                    times the spread between pair's alternations. --out appends.
 """
 import argparse
 import csv
@@ -56,6 +70,7 @@ ap.add_argument("--pmc-run")
 ap.add_argument("--pmc-summary")
 ap.add_argument("--crc64", action="store_true")
 ap.add_argument("--iov", action="store_true")
+ap.add_argument("--iov-seg", action="store_true")
 args = ap.parse_args()
 
 
@@ -244,8 +259,111 @@ def bench_iov():
     return res
 
 
-if args.iov:
-    line = json.dumps(bench_iov())
+def bench_iov_seg():
+    nmsg, big, small = 8192, 8192, 4096
+    nbig_m, nsmall_m = 8, 16
+    msg = nbig_m * big
+    nbig, nsmall, total = nmsg * nbig_m, nmsg * nsmall_m, nmsg * msg
+    src = torch.empty(total, dtype=torch.uint8, device="cuda")
+    dst = torch.zeros(total, dtype=torch.uint8, device="cuda")
+    ck.fill_splitmix(src, big, big, nbig, 0x5EED0101)
+    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).cuda()
+    # segment s of the stream of messages sits in 8 KiB slot (4099 s) mod nbig, block q in 4 KiB slot (8191 q) mod nsmall
+    slot = (np.arange(nbig, dtype=np.uint64) * np.uint64(4099)) % np.uint64(nbig)
+    bslot = (np.arange(nsmall, dtype=np.uint64) * np.uint64(8191)) % np.uint64(nsmall)
+
+    def iov(buf, slots, n):
+        a = np.empty((slots.size, 2), np.uint64)
+        a[:, 0] = np.uint64(buf.data_ptr()) + slots * np.uint64(n)
+        a[:, 1] = n
+        return i64(a)
+    big_start = i64(np.arange(nmsg + 1, dtype=np.uint64) * np.uint64(nbig_m))
+    small_start = i64(np.arange(nmsg + 1, dtype=np.uint64) * np.uint64(nsmall_m))
+    s_big, d_small = iov(src, slot, big), iov(dst, bslot, small)      # scatter into blocks
+    s_small, d_big = iov(src, bslot, small), iov(dst, slot, big)      # mirrored: blocks into segments
+    dt = torch.int64 if args.crc64 else torch.int32
+    out = torch.zeros(nmsg, dtype=dt, device="cuda")
+    seg = torch.zeros(nsmall, dtype=dt, device="cuda")
+    copy_iov = ck.copy_msg64_iov_n if args.crc64 else ck.copy_msg_iov_n
+    copy_seg = ck.copy_msg64_iov_seg_n if args.crc64 else ck.copy_msg_iov_seg_n
+    batch_iov = ck.batch64_iov if args.crc64 else ck.batch_iov
+
+    def pair():
+        copy_iov(s_big, big_start, nbig, d_small, small_start, nsmall, nmsg, out, stream=st)
+        batch_iov(d_small, nsmall, seg, stream=st)
+    arms = {
+        "plain": lambda: copy_iov(s_big, big_start, nbig, d_small, small_start, nsmall, nmsg, out, stream=st),
+        "pair": pair,
+        "seg_dst": lambda: copy_seg(s_big, big_start, nbig, d_small, small_start, nsmall, nmsg, ck.SEG_OF_DST, seg,
+                                    out, stream=st),
+        "plain_mirror": lambda: copy_iov(s_small, small_start, nsmall, d_big, big_start, nbig, nmsg, out, stream=st),
+        "seg_src": lambda: copy_seg(s_small, small_start, nsmall, d_big, big_start, nbig, nmsg, ck.SEG_OF_SRC, seg,
+                                    out, stream=st),
+    }
+    idx = lambda a: torch.from_numpy(a.astype(np.int64)).cuda()
+    stream_a = src.view(nbig, big)[idx(slot)].reshape(-1)
+    stream_m = src.view(nsmall, small)[idx(bslot)].reshape(-1)
+    # the CRC of every 4 KiB source block of the mirrored shape, by the batch kernel
+    src_blocks = torch.zeros(nsmall, dtype=dt, device="cuda")
+    batch_iov(s_small, nsmall, src_blocks, stream=st)
+    crcs, segs = {}, {}
+    for name, fn in arms.items():  # same CRCs, the right bytes landed, before anything is timed
+        dst.zero_()
+        out.fill_(-1)
+        seg.fill_(-1)
+        fn()
+        torch.cuda.synchronize()
+        if name in ("plain", "pair", "seg_dst"):
+            landed, want = dst.view(nsmall, small)[idx(bslot)].reshape(-1), stream_a
+        else:
+            landed, want = dst.view(nbig, big)[idx(slot)].reshape(-1), stream_m
+        assert torch.equal(landed, want), f"{name}: destination differs from the source stream"
+        crcs[name] = out.cpu().numpy().copy()
+        segs[name] = seg.cpu().numpy().copy()
+    assert np.array_equal(crcs["plain"], crcs["pair"]) and np.array_equal(crcs["plain"], crcs["seg_dst"]), \
+        "the arms' message CRCs differ"
+    assert np.array_equal(segs["pair"], segs["seg_dst"]), "the block CRCs of pair and seg_dst differ"
+    assert np.array_equal(crcs["plain_mirror"], crcs["seg_src"]), "the mirrored arms' message CRCs differ"
+    assert np.array_equal(segs["seg_src"], src_blocks.cpu().numpy()), "seg_src differs from batch_iov over the source blocks"
+    del stream_a, stream_m
+    means = {k: [] for k in arms}
+    times = {k: [] for k in arms}
+    for r in range(args.rounds):
+        for name in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+            fn = arms[name]
+            for _ in range(args.warmup):
+                fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.reps + 1)]
+            ev[0].record(st)
+            for k in range(args.reps):
+                fn()
+                ev[k + 1].record(st)
+            torch.cuda.synchronize()
+            t = [ev[k].elapsed_time(ev[k + 1]) for k in range(args.reps)]
+            times[name] += t
+            means[name].append(float(np.mean(t)))
+    gib = total / 2.0**30
+    res = {"shape": "iov_seg", "crc": "crc64ecma" if args.crc64 else "crc32c", "nmsg": nmsg, "segments": nbig_m,
+           "segment_bytes": big, "blocks": nsmall_m, "block_bytes": small, "rounds": args.rounds, "reps": args.reps,
+           "warmup": args.warmup}
+    for name in arms:
+        ms = np.asarray(times[name])
+        res[name] = {"ms_mean": round(float(ms.mean()), 5), "ms_median": round(float(np.median(ms)), 5),
+                     "payload_GiBps_mean": round(gib / (ms.mean() * 1e-3), 1),
+                     "round_means_ms": [round(m, 5) for m in means[name]],
+                     "spread_ms": round(max(means[name]) - min(means[name]), 5)}
+    a, p, b = res["plain"]["ms_mean"], res["pair"]["ms_mean"], res["seg_dst"]["ms_mean"]
+    res["ratio_seg_dst_over_pair"] = round(b / p, 4)
+    res["ratio_seg_dst_over_plain"] = round(b / a, 4)
+    res["ratio_seg_src_over_plain"] = round(res["seg_src"]["ms_mean"] / a, 4)
+    res["ratio_seg_src_over_plain_mirror"] = round(res["seg_src"]["ms_mean"] / res["plain_mirror"]["ms_mean"], 4)
+    res["margin_over_pair_spread"] = round((p - b) / max(res["pair"]["spread_ms"], 1e-9), 2)
+    res["faster_3x"] = bool(p - b > 3 * res["pair"]["spread_ms"])
+    return res
+
+
+if args.iov or args.iov_seg:
+    line = json.dumps(bench_iov_seg() if args.iov_seg else bench_iov())
     print(line, flush=True)
     if args.out:
         with open(args.out, "a") as f:
