@@ -274,6 +274,34 @@ int photon_crc32c_trim_batch(const photon_crc_component* d_all, const photon_crc
                              uint32_t* d_nerr, void* stream);
 int photon_crc32c_extend_device(const void* d_data, uint64_t nbytes, uint32_t seed, uint32_t* d_out, void* stream);
 
+/* Copy + CRC-32C of ONE long buffer in ONE launch over the whole device:
+ * [d_dst, d_dst + nbytes) receives the nbytes at src, and *d_out =
+ * crc32c_extend(src, nbytes, seed), bit-identical to
+ * photon_crc32c_extend_device on the same bytes. The copy + CRC calls at (iv)
+ * give one buffer to one lane group, which is right for many small payloads;
+ * this one cuts the buffer over the chip on extend_device's plan (chunks on
+ * a grid anchored at a 4 KiB boundary of the source; every size takes it, so
+ * photon_crc_set_long_shape applies and photon_crc_set_mid_kernel does not).
+ * Contract (iv) holds: the source is HBM, or pinned / registered host memory
+ * read in place; the destination is device-accessible; source and
+ * destination must not overlap (the caller's responsibility, not checked);
+ * no byte outside [d_dst, d_dst + nbytes) is written and nothing is
+ * read-modify-written; any alignment is correct; with (d_dst - src) % 16 == 0
+ * the payload is read exactly once, otherwise each chunk is copied first and
+ * checksummed from the cache. Asynchronous on `stream`; nothing is allocated
+ * or synchronised beyond what extend_device does, and a call is capturable
+ * into a graph under extend_device's rules (the reduce state is owned by the
+ * graph, one replay at a time). No CPU fallback.
+ *   - A null d_out, or a null src or d_dst with nbytes > 0, gives -EINVAL.
+ *   - nbytes == 0 (src and d_dst may be null) writes the seed to *d_out and
+ *     touches nothing else.
+ * An object assembled from a few large parts: one call per part with seed 0
+ * into dst + offset, on one stream; the outputs are the part CRCs, and the
+ * object's CRC is their crc32c_combine fold (on the host, or by
+ * photon_crc32c_combine_batch). */
+int photon_crc32c_copy_extend_device(const void* src, void* d_dst, uint64_t nbytes,
+                                     uint32_t seed, uint32_t* d_out, void* stream);
+
 /* (many GPUs) ONE logical buffer whose bytes lie on several devices of this
  * process: span i = [d_data, d_data + nbytes) on `device`, the spans in
  * buffer order. Every span runs photon_crc32c_extend_device (from seed 0) on
@@ -408,6 +436,13 @@ int photon_crc64ecma_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uin
  * state and capture rules. */
 int photon_crc64ecma_extend_device(const void* d_data, uint64_t nbytes, uint64_t seed, uint64_t* d_out,
                                    void* stream);
+/* photon_crc32c_copy_extend_device for CRC-64/ECMA: the same arguments, plan
+ * and contract; *d_out = crc64ecma_extend(src, nbytes, seed), bit-identical
+ * to photon_crc64ecma_extend_device on the same bytes. An OSS object part of
+ * tens of MiB to GiB is landed and given its x-oss-hash-crc64ecma by one
+ * call; the object's CRC is the parts' crc64ecma_combine fold. */
+int photon_crc64ecma_copy_extend_device(const void* src, void* d_dst, uint64_t nbytes,
+                                        uint64_t seed, uint64_t* d_out, void* stream);
 /* photon_crc32c_extend_spans for CRC-64/ECMA (crc64ecma_combine's identity:
  * the inverted CRC folds the same way). */
 int photon_crc64ecma_extend_spans(const photon_crc_span* spans, int nspans, uint64_t seed, uint64_t* h_result);

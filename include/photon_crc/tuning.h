@@ -58,7 +58,9 @@ int photon_crc_set_mid_kernel(int on);
  * measurements behind each step): CRC-32C 64 lanes x 2 rounds, 32 x 2 from
  * 512 MiB, 64 x 4 from 1.5 GiB, 64 x 2 from 3 GiB; CRC-64 64 lanes x 1
  * round, 64 x 2 from 512 MiB, 32 x 2 from 1 GiB, 64 x 4 from 1.5 GiB, 64 x 2
- * from 3 GiB. */
+ * from 3 GiB. Also the shape of photon_crc32c_copy_extend_device /
+ * photon_crc64ecma_copy_extend_device, at every size (the mid kernel switch
+ * above does not apply to them). */
 int photon_crc_set_long_shape(int lanes, int rounds);
 
 /* CRC-64 batches of whole steps (aligned strided, one seed, nbytes a

@@ -112,6 +112,8 @@ def _declare(L):
        vp, vp, vp)
     fn("photon_crc64ecma_copy_msg_iov_seg_n", ctypes.c_int, vp, vp, u64, vp, vp, u64, u64, vp, u64, vp, ctypes.c_int,
        vp, vp, vp, vp)
+    fn("photon_crc32c_copy_extend_device", ctypes.c_int, vp, vp, u64, u32, vp, vp)
+    fn("photon_crc64ecma_copy_extend_device", ctypes.c_int, vp, vp, u64, u64, vp, vp)
     # include/photon_crc/checked_batch.h
     fn("photon_crc_pinned_allocate", ctypes.c_int, vp, PhotonRange, ctypes.POINTER(vp))
     fn("photon_crc_pinned_deallocate", ctypes.c_int, vp, vp)

@@ -32,6 +32,7 @@ __all__ = [
     "copy_batch64_strided", "copy_batch64_iov", "gather64_msg_n",
     "copy_msg_iov_n", "copy_msg64_iov_n",
     "copy_msg_iov_seg_n", "copy_msg64_iov_seg_n", "SEG_OF_SRC", "SEG_OF_DST",
+    "copy_extend_device", "copy_extend64_device",
     "batch64_strided", "batch64_iov", "combine64_batch", "trim64_batch", "batch64_msg_n", "host_batch64_strided", "extend64_device", "extend_spans", "extend64_spans", "Span", "combine_batch", "fill_splitmix", "read_stream", "IOVEC_DTYPE",
 ]
 
@@ -497,6 +498,20 @@ def trim_batch(all_, prefix, suffix, count, out, nerr=None, stream=None):
 def extend_device(data, nbytes, seed, out, stream=None):
     """*out = crc32c_extend(data, nbytes, seed) for one long device buffer. Async."""
     _check(lib().photon_crc32c_extend_device(_ptr(data), nbytes, seed & 0xFFFFFFFF, _ptr(out), _stream(stream)))
+
+
+def copy_extend_device(src, dst, nbytes, seed, out, stream=None):
+    """Copy + CRC-32C of one long buffer over the whole device: dst receives the nbytes at src and
+    *out = crc32c_extend(src, nbytes, seed), what extend_device gives for the same bytes. Any
+    alignment; the payload is read once when (dst - src) % 16 == 0. nbytes == 0 writes the seed. Async."""
+    _check(lib().photon_crc32c_copy_extend_device(_ptr(src), _ptr(dst), nbytes, seed & 0xFFFFFFFF, _ptr(out),
+                                                  _stream(stream)))
+
+
+def copy_extend64_device(src, dst, nbytes, out, seed=0, stream=None):
+    """copy_extend_device for CRC-64/ECMA: *out = crc64ecma_extend(src, nbytes, seed). Async."""
+    _check(lib().photon_crc64ecma_copy_extend_device(_ptr(src), _ptr(dst), nbytes, seed & 0xFFFFFFFFFFFFFFFF,
+                                                     _ptr(out), _stream(stream)))
 
 
 class Span(ctypes.Structure):

@@ -1290,6 +1290,10 @@ int extend64_device_big(int dev, const void* d_data, uint64_t nbytes, uint64_t s
                         int cus, uint32_t tag);
 int extend64_device_long(const void* d_data, uint64_t nbytes, uint64_t seed, uint64_t* d_out, hipStream_t st,
                          int cus, uint32_t tag);
+int copy_extend_device_long(const void* src, void* d_dst, uint64_t nbytes, uint32_t seed, uint32_t* d_out,
+                            hipStream_t st, int cus);
+int copy_extend64_device_long(const void* src, void* d_dst, uint64_t nbytes, uint64_t seed, uint64_t* d_out,
+                              hipStream_t st, int cus);
 
 // For the other translation units of the library (internal.h).
 int report_error(int code, const char* what) { return fail(code, what); }
@@ -2134,9 +2138,41 @@ int extend64_device_long(const void* d_data, uint64_t nbytes, uint64_t seed, uin
         return hipGetLastError();
     });
 }
+
+// photon_crc64ecma_copy_extend_device: extend64_device_long's plan, powers and
+// state with the copying kernel. Every size comes here (the plan's `small`
+// branch serves spans up to 256 KiB).
+int copy_extend64_device_long(const void* src, void* d_dst, uint64_t nbytes, uint64_t seed, uint64_t* d_out,
+                              hipStream_t st, int cus) {
+    const LongPlan lp = long_plan(src, nbytes, cus, true);
+    const LongPowers& pw = long_powers(lp, true);
+    CopyLong64Args a{};
+    long_args64(&a, lp, pw, src, seed, d_out);
+    a.dst = static_cast<uint8_t*>(d_dst);
+    HeavyLaunch heavy(st);
+    return long_launch(st, lp.grid, "crc64_copy_long_kernel launch", [&](void* state, uint64_t base, uint32_t reset) {
+        a.acc = static_cast<uint64_t*>(state);
+        a.tbase = base;
+        a.treset = reset;
+        if (lp.lanes == 32)
+            hipLaunchKernelGGL((crc64_copy_long_kernel<32>), dim3(lp.grid), dim3(kBlock), 0, st, a, lane_consts64(32));
+        else
+            hipLaunchKernelGGL((crc64_copy_long_kernel<64>), dim3(lp.grid), dim3(kBlock), 0, st, a, lane_consts64(64));
+        return hipGetLastError();
+    });
+}
 }  // namespace pcrc
 
 extern "C" {
+
+int photon_crc64ecma_copy_extend_device(const void* src, void* d_dst, uint64_t nbytes, uint64_t seed, uint64_t* d_out,
+                                        void* stream) {
+    if (!d_out || ((!src || !d_dst) && nbytes)) return fail(-EINVAL, "null source, destination or output");
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    return pcrc::copy_extend64_device_long(src, d_dst, nbytes, seed, d_out, static_cast<hipStream_t>(stream), cus);
+}
 
 int photon_crc32c_combine_batch(const uint32_t* d_crc1, const uint32_t* d_crc2, const uint32_t* d_len2,
                                 uint64_t count, uint32_t* d_out, void* stream) {
@@ -2272,7 +2308,43 @@ int extend_device_long(const void* d_data, uint64_t nbytes, uint32_t seed, uint3
         return hipGetLastError();
     });
 }
+
+// photon_crc32c_copy_extend_device: extend_device_long's plan, powers and
+// state with the copying kernel. Every size comes here (the plan's `small`
+// branch serves spans up to 256 KiB).
+int copy_extend_device_long(const void* src, void* d_dst, uint64_t nbytes, uint32_t seed, uint32_t* d_out,
+                            hipStream_t st, int cus) {
+    const LongPlan lp = long_plan(src, nbytes, cus, false);
+    const LongPowers& pw = long_powers(lp, false);
+    CopyLongArgs a{};
+    long_args(&a, lp, pw, src, seed, d_out);
+    a.dst = static_cast<uint8_t*>(d_dst);
+    HeavyLaunch heavy(st);
+    return long_launch(st, lp.grid, "crc32c_copy_long_kernel launch", [&](void* state, uint64_t base, uint32_t reset) {
+        a.acc = static_cast<uint32_t*>(state);
+        a.tbase = base;
+        a.treset = reset;
+        if (lp.lanes == 32)
+            hipLaunchKernelGGL((crc32c_copy_long_kernel<32, 4>), dim3(lp.grid), dim3(kBlock), 0, st, a,
+                               lane_consts(32));
+        else
+            hipLaunchKernelGGL((crc32c_copy_long_kernel<64, 4>), dim3(lp.grid), dim3(kBlock), 0, st, a,
+                               lane_consts(64));
+        return hipGetLastError();
+    });
+}
 }  // namespace pcrc
+
+extern "C" {
+int photon_crc32c_copy_extend_device(const void* src, void* d_dst, uint64_t nbytes, uint32_t seed, uint32_t* d_out,
+                                     void* stream) {
+    if (!d_out || ((!src || !d_dst) && nbytes)) return fail(-EINVAL, "null source, destination or output");
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    return pcrc::copy_extend_device_long(src, d_dst, nbytes, seed, d_out, static_cast<hipStream_t>(stream), cus);
+}
+}  // extern "C"
 
 namespace pcrc {
 namespace {

@@ -2063,9 +2063,25 @@ __device__ __forceinline__ void long_finish(const LongArgs& a, uint32_t acc, uin
 // attribution, results NOT the CRC unless noted: 8 = the reduce WITH the
 // agent-scope release/acquire (correct), 16 = no cross-workgroup reduce
 // (each workgroup writes its value), 32 = no wave and workgroup factors.
-template <int G, int U, bool STAMP = false, int ABL = 0>
+// COPY (crc32c_copy_long_kernel): the same walk, and the
+// chunk at p is also landed at dst + (p - a.data) by the copying unit
+// (copy_begin + buffer_crc<.., COPY>). What follows from the cut:
+//   - with PCRC_LONG_MERGE_HEAD body chunk 0 starts at the unaligned a.data
+//     and is head + chunk bytes; its first block is stored by store_head,
+//     bytes s0..15 only, so nothing before dst is written;
+//   - an empty leading slot (n == 0) is a tiny buffer of no bytes: it stores
+//     nothing (a wave of empty slots skips the round altogether);
+//   - a buffer wholly before the first 4 KiB boundary is the head slot alone
+//     (nchunks == 0, up to 4095 bytes from the unaligned a.data);
+//   - a last chunk under 64 bytes takes the unit's tiny path (byte k stored
+//     by lane k mod G), also when dst is not co-aligned with the source;
+//   - every other chunk starts on a 4 KiB boundary of the source, so with
+//     (dst - data) % 16 == 0 no 16-byte destination block is shared between
+//     two chunks; otherwise group_copy writes each chunk's bytes exactly
+//     once with byte stores at its two ends.
+template <int G, int U, bool STAMP = false, int ABL = 0, bool COPY = false>
 __device__ __forceinline__ void long_run(const LongArgs& a, const LaneConsts& kc, uint32_t* lds, uint32_t* red,
-                                         uint64_t* t) {
+                                         uint64_t* t, uint8_t* dst = nullptr) {
     uint64_t t0 = 0, c0 = 0, t_tab = 0;
     if constexpr (STAMP) {
         t0 = __builtin_amdgcn_s_memrealtime();
@@ -2103,8 +2119,14 @@ __device__ __forceinline__ void long_run(const LongArgs& a, const LaneConsts& kc
         long_slot(a, v, &p, &n, &last, &head);
         const uint32_t seed = head ? a.seed : 0u;  // the head carries the seed
         uint32_t crc = 0;
-        if (__ballot(n != 0 || seed != 0))  // a wave with only empty slots skips the round's loads
-            crc = buffer_crc<G, U, PCRC_LONG_LEAD>(lds, p, n, seed, gl, la);
+        if (__ballot(n != 0 || seed != 0)) {  // a wave with only empty slots skips the round's loads
+            if constexpr (COPY) {
+                const CopyTo ct = copy_begin<G>(p, dst + (p - a.data), n, gl);
+                crc = buffer_crc<G, U, PCRC_LONG_LEAD, true>(lds, p, n, seed, gl, la, true, ct);
+            } else {
+                crc = buffer_crc<G, U, PCRC_LONG_LEAD>(lds, p, n, seed, gl, la);
+            }
+        }
         // The last chunk stays out of the Horner fold (it enters with factor
         // 1); keeping a general multiply out of this loop keeps the row loop's
         // schedule (round 3: a 32-step multiply here made the compiler reduce
@@ -2138,6 +2160,19 @@ __global__ __launch_bounds__(kBlock) void crc32c_long_kernel(LongArgs a, LaneCon
     __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
     __shared__ uint32_t red[2 * kWaves];
     long_run<G, U>(a, kc, lds, red, nullptr);
+}
+
+// photon_crc32c_copy_extend_device: the long kernel that also lands the
+// buffer at dst (long_run<.., COPY>), on the same plan and reduce state.
+struct CopyLongArgs : LongArgs {
+    uint8_t* dst;  // receives [data, data + nbytes)
+};
+
+template <int G, int U>
+__global__ __launch_bounds__(kBlock) void crc32c_copy_long_kernel(CopyLongArgs a, LaneConsts kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
+    __shared__ uint32_t red[2 * kWaves];
+    long_run<G, U, false, 0, true>(a, kc, lds, red, nullptr, a.dst);
 }
 
 // ------------------------------------------------ one small buffer (latency)

@@ -1206,9 +1206,13 @@ __device__ __forceinline__ uint64_t mul_wave64(uint64_t v, uint64_t bw, uint32_t
 }
 
 // STAMP (probe builds): t0, tables built, basis words done, rounds done, end.
-template <int G, bool STAMP = false>
+// COPY (crc64_copy_long_kernel): the chunk at p is also landed
+// at dst + (p - a.data) by the copying unit (copy_begin + buffer_reg64<G,
+// true>); the cases that follow from the cut are written at crc32c_kernels.h
+// long_run. The register is broadcast within the group as before.
+template <int G, bool STAMP = false, bool COPY = false>
 __device__ __forceinline__ void crc64_long_run(const Long64Args& a, const LaneConsts64& kc, uint32_t* lds,
-                                               uint64_t* red, uint64_t* t) {
+                                               uint64_t* red, uint64_t* t, uint8_t* dst = nullptr) {
     uint64_t ts[5] = {0, 0, 0, 0, 0};
     if constexpr (STAMP) ts[0] = __builtin_amdgcn_s_memrealtime();
     load_tables64<G>(lds, kc);
@@ -1232,10 +1236,14 @@ __device__ __forceinline__ void crc64_long_run(const Long64Args& a, const LaneCo
     };
     // The wave's and (wave 0) the workgroup's factor: basis words computed
     // here, one per lane, before any chunk; X's for the 32-lane form.
-    const uint64_t bw_z = basis_word64_lds(lds, a.zt[wave], lane, la.r8);
-    const uint64_t bw_f = wave == 0 ? basis_word64_lds(lds, a.ft[blockIdx.x], lane, la.r8) : 0ull;
-    const uint64_t bx0 = G == 32 ? basis_word64_lds(lds, a.x, l, la.r8) : 0ull;
-    const uint64_t bx1 = G == 32 ? basis_word64_lds(lds, a.x, l + 32, la.r8) : 0ull;
+    // kLate (the copying 32-lane build): the four words are
+    // computed after the round loop instead -- held across it they took the
+    // build past 128 VGPRs (32 B of scratch); still outside the row loop.
+    constexpr bool kLate = COPY && G == 32;
+    const uint64_t bw_z = kLate ? 0ull : basis_word64_lds(lds, a.zt[wave], lane, la.r8);
+    const uint64_t bw_f = !kLate && wave == 0 ? basis_word64_lds(lds, a.ft[blockIdx.x], lane, la.r8) : 0ull;
+    const uint64_t bx0 = !kLate && G == 32 ? basis_word64_lds(lds, a.x, l, la.r8) : 0ull;
+    const uint64_t bx1 = !kLate && G == 32 ? basis_word64_lds(lds, a.x, l + 32, la.r8) : 0ull;
     // Complete them here: left to the scheduler, their LDS lookups were
     // spread into the round loop and slowed it (1 GiB, 32 lanes: 0.192 vs
     // 0.169 ms with this barrier, repo:profiles/r04f_ab_long_basis_lds.jsonl).
@@ -1250,7 +1258,12 @@ __device__ __forceinline__ void crc64_long_run(const Long64Args& a, const LaneCo
         long_slot(a, v, &p, &n, &last, &head);
         uint64_t reg = 0;
         if (__ballot(n != 0 || head)) {
-            reg = buffer_reg64<G>(lds, p, n, head ? ~a.seed : 0ull, gl, lane, la);  // valid on gl == 0
+            if constexpr (COPY) {
+                const CopyTo ct = copy_begin<G>(p, dst + (p - a.data), n, gl);
+                reg = buffer_reg64<G, true>(lds, p, n, head ? ~a.seed : 0ull, gl, lane, la, true, ct);
+            } else {
+                reg = buffer_reg64<G>(lds, p, n, head ? ~a.seed : 0ull, gl, lane, la);  // valid on gl == 0
+            }
             reg = __shfl(reg, lane & ~(uint32_t)(G - 1), 64);                        // the whole group
         }
         const uint64_t m = mul_group(acc, bw0, bw1);
@@ -1258,16 +1271,24 @@ __device__ __forceinline__ void crc64_long_run(const Long64Args& a, const LaneCo
         lastc = last ? reg : lastc;
     }
     if constexpr (STAMP) ts[3] = __builtin_amdgcn_s_memrealtime();
+    uint64_t fz = bw_z, ff = bw_f, fx0 = bx0, fx1 = bx1;
+    if constexpr (kLate) {
+        asm volatile("" ::"v"(acc), "v"(lastc));  // the rounds are complete
+        fz = basis_word64_lds(lds, a.zt[wave], lane, la.r8);
+        ff = wave == 0 ? basis_word64_lds(lds, a.ft[blockIdx.x], lane, la.r8) : 0ull;
+        fx0 = basis_word64_lds(lds, a.x, l, la.r8);
+        fx1 = basis_word64_lds(lds, a.x, l + 32, la.r8);
+    }
     uint64_t v = acc;
     if constexpr (G == 32) {  // acc_0 * X ^ acc_1
-        const uint64_t m = mul_group(acc, bx0, bx1);
+        const uint64_t m = mul_group(acc, fx0, fx1);
         v = lane < 32 ? m : acc;
         v ^= ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), 32, 64) << 32) |
              (uint32_t)__shfl_xor((int)(uint32_t)v, 32, 64);
         lastc ^= ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(lastc >> 32), 32, 64) << 32) |
                  (uint32_t)__shfl_xor((int)(uint32_t)lastc, 32, 64);
     }
-    v = mul_wave64(v, bw_z, lane);  // * Z^(15 - w)
+    v = mul_wave64(v, fz, lane);  // * Z^(15 - w)
     if (lane == 0) {
         red[wave] = v;
         red[kWaves + wave] = lastc;
@@ -1280,7 +1301,7 @@ __device__ __forceinline__ void crc64_long_run(const Long64Args& a, const LaneCo
             u ^= red[w];
             e ^= red[kWaves + w];
         }
-        u = mul_wave64(u, bw_f, lane) ^ e;  // * J Y^(grid - 1 - b), then the last chunk
+        u = mul_wave64(u, ff, lane) ^ e;  // * J Y^(grid - 1 - b), then the last chunk
         long_reduce(u, a.acc, a.out, [](uint64_t x) { return ~x; }, a.tbase, a.treset,
                     a.out_tag);  // crc.cpp:119-122: inverted out
     }
@@ -1295,6 +1316,19 @@ __global__ __launch_bounds__(kBlock) void crc64_long_kernel(Long64Args a, LaneCo
     __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
     __shared__ uint64_t red[2 * kWaves];
     crc64_long_run<G>(a, kc, lds, red, nullptr);
+}
+
+// photon_crc64ecma_copy_extend_device: the long kernel that also lands the
+// buffer at dst (crc64_long_run<G, false, true>).
+struct CopyLong64Args : Long64Args {
+    uint8_t* dst;  // receives [data, data + nbytes)
+};
+
+template <int G>
+__global__ __launch_bounds__(kBlock) void crc64_copy_long_kernel(CopyLong64Args a, LaneConsts64 kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
+    __shared__ uint64_t red[2 * kWaves];
+    crc64_long_run<G, false, true>(a, kc, lds, red, nullptr, a.dst);
 }
 
 // photon_crc64ecma_extend_device for buffers whose 16-byte block span is at

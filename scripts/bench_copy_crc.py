@@ -49,6 +49,20 @@ the ratio (b)/(a), and the spread between the alternations of each arm;
                     through copy_msg_iov_n and through the new call with a CRC per
                     source block. "faster_3x" is true when pair - seg_dst exceeds three
                     times the spread between pair's alternations. --out appends.
+  --long : copy + CRC of ONE long buffer over the whole device
+                    (photon_crc32c_copy_extend_device; with --crc64 the CRC-64 call), the
+                    same method, one JSON line per size (--sizes, MiB), source at buf+1,
+                    destination at dbuf+1 (the reference's perf shape, co-aligned) and one
+                    last row not co-aligned (destination at dbuf+10, no claim): "pair" =
+                    photon_crc_memcpy_async, then extend_device over the copy (3 bytes
+                    moved per payload byte); "fused" = the new call (2 bytes per payload
+                    byte; floor for fused/pair ~ 0.67); "pieces" = copy_batch_strided over
+                    64 KiB pieces of the same bytes, then combine_series_device (CRC-64
+                    has no device fold: its pieces arm is the piece batch alone, the fold
+                    left to the host and not timed). "faster_3x" is true when pair - fused
+                    exceeds three times the spread between pair's alternations; "within" is
+                    true when |fused - pieces| is at most the larger of 3 % of pieces and
+                    three times the spread of pieces. --out appends.
 """
 import argparse
 import csv
@@ -71,6 +85,8 @@ ap.add_argument("--pmc-summary")
 ap.add_argument("--crc64", action="store_true")
 ap.add_argument("--iov", action="store_true")
 ap.add_argument("--iov-seg", action="store_true")
+ap.add_argument("--long", action="store_true")
+ap.add_argument("--sizes", default="64,256,1024", help="--long: payload sizes in MiB")
 args = ap.parse_args()
 
 
@@ -361,6 +377,100 @@ def bench_iov_seg():
     res["faster_3x"] = bool(p - b > 3 * res["pair"]["spread_ms"])
     return res
 
+
+def bench_long(mib, delta):
+    n, piece = mib << 20, 65536
+    count = n // piece
+    assert count * piece == n
+    src = torch.empty(n + 4096, dtype=torch.uint8, device="cuda")
+    dst = torch.zeros(n + 4096, dtype=torch.uint8, device="cuda")
+    assert src.data_ptr() % 4096 == 0 and dst.data_ptr() % 4096 == 0
+    ck.fill_splitmix(src, src.numel(), src.numel(), 1, 0x5EED0201)
+    sp, dp = src.data_ptr() + 1, dst.data_ptr() + 1 + delta
+    dt = torch.int64 if args.crc64 else torch.int32
+    out = torch.zeros(1, dtype=dt, device="cuda")
+    parts = torch.zeros(count, dtype=dt, device="cuda")
+
+    def pair():
+        ck._check(lib().photon_crc_memcpy_async(dp, sp, n, st.cuda_stream))
+        if args.crc64:
+            ck.extend64_device(dp, n, out, stream=st)
+        else:
+            ck.extend_device(dp, n, 0, out, stream=st)
+
+    def fused():
+        if args.crc64:
+            ck.copy_extend64_device(sp, dp, n, out, stream=st)
+        else:
+            ck.copy_extend_device(sp, dp, n, 0, out, stream=st)
+
+    def pieces():
+        if args.crc64:
+            ck.copy_batch64_strided(sp, piece, dp, piece, piece, count, parts, stream=st)
+        else:
+            ck.copy_batch_strided(sp, piece, dp, piece, piece, count, parts, stream=st)
+            ck.combine_series_device(parts, piece, count, out, stream=st)
+    arms = {"pair": pair, "fused": fused, "pieces": pieces}
+    crcs = {}
+    for name, fn in arms.items():  # same CRC, same bytes landed, before anything is timed
+        dst.zero_()
+        out.fill_(-1)
+        fn()
+        torch.cuda.synchronize()
+        assert torch.equal(dst[1 + delta:1 + delta + n], src[1:1 + n]), f"{name}: destination differs from the source"
+        assert not bool(dst[:1 + delta].any()) and not bool(dst[1 + delta + n:].any()), f"{name}: wrote outside"
+        if name == "pieces" and args.crc64:
+            crcs[name] = ck.crc64ecma_combine_series([int(x) for x in parts.cpu().numpy().view(np.uint64)], piece)
+        else:
+            crcs[name] = int(out.cpu().numpy().view(np.uint64 if args.crc64 else np.uint32)[0])
+    assert crcs["pair"] == crcs["fused"] == crcs["pieces"], f"the arms' CRCs differ: {crcs}"
+    means = {k: [] for k in arms}
+    times = {k: [] for k in arms}
+    for r in range(args.rounds):
+        for name in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+            fn = arms[name]
+            for _ in range(args.warmup):
+                fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.reps + 1)]
+            ev[0].record(st)
+            for k in range(args.reps):
+                fn()
+                ev[k + 1].record(st)
+            torch.cuda.synchronize()
+            t = [ev[k].elapsed_time(ev[k + 1]) for k in range(args.reps)]
+            times[name] += t
+            means[name].append(float(np.mean(t)))
+    gib = n / 2.0**30
+    res = {"shape": "long", "crc": "crc64ecma" if args.crc64 else "crc32c", "MiB": mib, "src": "buf+1",
+           "dst": f"dbuf+{1 + delta}", "co_aligned": delta % 16 == 0, "piece_bytes": piece,
+           "pieces_fold": "host, not timed" if args.crc64 else "combine_series_device", "rounds": args.rounds,
+           "reps": args.reps, "warmup": args.warmup}
+    for name in arms:
+        ms = np.asarray(times[name])
+        res[name] = {"ms_mean": round(float(ms.mean()), 5), "ms_median": round(float(np.median(ms)), 5),
+                     "payload_GiBps_mean": round(gib / (ms.mean() * 1e-3), 1),
+                     "round_means_ms": [round(m, 5) for m in means[name]],
+                     "spread_ms": round(max(means[name]) - min(means[name]), 5)}
+    a, b, c = res["pair"]["ms_mean"], res["fused"]["ms_mean"], res["pieces"]["ms_mean"]
+    res["ratio_fused_over_pair"] = round(b / a, 4)
+    res["margin_over_pair_spread"] = round((a - b) / max(res["pair"]["spread_ms"], 1e-9), 2)
+    res["faster_3x"] = bool(a - b > 3 * res["pair"]["spread_ms"])
+    res["ratio_fused_over_pieces"] = round(b / c, 4)
+    res["allowed_ms"] = round(max(0.03 * c, 3 * res["pieces"]["spread_ms"]), 5)
+    res["within"] = bool(abs(b - c) <= res["allowed_ms"])
+    res["fused_slower_than_pieces"] = bool(b - c > res["allowed_ms"])
+    return res
+
+
+if args.long:
+    sizes = [int(x) for x in args.sizes.split(",")]
+    for mib, delta in [(m, 0) for m in sizes] + [(max(sizes), 9)]:
+        line = json.dumps(bench_long(mib, delta))
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+    sys.exit(0)
 
 if args.iov or args.iov_seg:
     line = json.dumps(bench_iov_seg() if args.iov_seg else bench_iov())
