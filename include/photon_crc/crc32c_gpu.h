@@ -295,10 +295,10 @@ int photon_crc32c_extend_device(const void* d_data, uint64_t nbytes, uint32_t se
  *   - A null d_out, or a null src or d_dst with nbytes > 0, gives -EINVAL.
  *   - nbytes == 0 (src and d_dst may be null) writes the seed to *d_out and
  *     touches nothing else.
- * An object assembled from a few large parts: one call per part with seed 0
- * into dst + offset, on one stream; the outputs are the part CRCs, and the
- * object's CRC is their crc32c_combine fold (on the host, or by
- * photon_crc32c_combine_batch). */
+ * An object assembled from parts: one call per part with seed 0 into
+ * dst + offset, on one stream; the outputs are the part CRCs, and the
+ * object's CRC is their fold by ONE photon_crc32c_fold_parts_n call on the
+ * same stream (below; no synchronisation, parts of any length). */
 int photon_crc32c_copy_extend_device(const void* src, void* d_dst, uint64_t nbytes,
                                      uint32_t seed, uint32_t* d_out, void* stream);
 
@@ -319,7 +319,8 @@ int photon_crc32c_extend_spans(const photon_crc_span* spans, int nspans, uint32_
 
 /* Route the drop-in entry points to the device when handed device memory:
  * with on != 0, crc32c_auto / crc32c_series_auto / crc32c_combine_series_auto
- * (crc.cpp:126-134) and crc64ecma_auto point to wrappers that ask HIP whether the data pointer
+ * (crc.cpp:126-134) and crc64ecma_auto / crc64ecma_series_auto /
+ * crc64ecma_combine_series_auto point to wrappers that ask HIP whether the data pointer
  * is device memory (hipMemoryTypeDevice) and, if so, run the calls above
  * synchronously on that pointer's device, else call the host engine. A
  * routed call runs on a non-blocking stream leased from a per-device pool
@@ -440,12 +441,75 @@ int photon_crc64ecma_extend_device(const void* d_data, uint64_t nbytes, uint64_t
  * and contract; *d_out = crc64ecma_extend(src, nbytes, seed), bit-identical
  * to photon_crc64ecma_extend_device on the same bytes. An OSS object part of
  * tens of MiB to GiB is landed and given its x-oss-hash-crc64ecma by one
- * call; the object's CRC is the parts' crc64ecma_combine fold. */
+ * call; the object's CRC is the parts' fold: one
+ * photon_crc64ecma_fold_parts_n call on the same stream (below). */
 int photon_crc64ecma_copy_extend_device(const void* src, void* d_dst, uint64_t nbytes,
                                         uint64_t seed, uint64_t* d_out, void* stream);
 /* photon_crc32c_extend_spans for CRC-64/ECMA (crc64ecma_combine's identity:
  * the inverted CRC folds the same way). */
 int photon_crc64ecma_extend_spans(const photon_crc_span* spans, int nspans, uint64_t seed, uint64_t* h_result);
+
+/* photon_crc32c_series_device / photon_crc32c_combine_series_device for
+ * CRC-64/ECMA, with the semantics of this library's host definitions
+ * (crc64_cpu.cpp; the reference declares crc64ecma_series /
+ * crc64ecma_combine_series and never defines them):
+ *   series:         d_crc_parts[i] = crc64ecma(d_buffer + i*part_size,
+ *                   part_size, 0), for every part_size (no part_size < 8
+ *                   quirk); part_size == 0 writes zeros and reads nothing;
+ *                   n_parts == 0 returns 0 and touches nothing;
+ *   combine_series: *d_result = crc64ecma_combine_series(d_crc, part_size,
+ *                   n_parts) = XOR_i crc[i] * K^(n-1-i), K = x^(8*part_size)
+ *                   (K = 1 for part_size 0); n_parts == 0 gives 0.
+ * Asynchronous on `stream`; a null required pointer gives -EINVAL. */
+int photon_crc64ecma_series_device(const void* d_buffer, uint32_t part_size, uint32_t n_parts,
+                                   uint64_t* d_crc_parts, void* stream);
+int photon_crc64ecma_combine_series_device(const uint64_t* d_crc, uint32_t part_size, uint32_t n_parts,
+                                           uint64_t* d_result, void* stream);
+
+/* Fold the CRCs of objects' parts into the objects' CRCs on the device: the
+ * step after one photon_crc32c_copy_extend_device /
+ * photon_crc64ecma_copy_extend_device call per part (seed 0), on the same
+ * stream, with nothing in between. Object m is the parts s in
+ * [d_obj_start[m], d_obj_start[m+1]) of the nparts (CRC, length) pairs
+ * d_crc[s], d_len[s]; d_obj_start has nobj + 1 entries and its last must
+ * equal nparts (the caller's duty, as in the _msg_n calls; no part outside
+ * [0, nparts) is read in any case). A null d_obj_start means ONE object of all
+ * nparts parts, and nobj must then be 1. With acc = seed_m (d_seeds[m], or
+ * seed0 when d_seeds is null):
+ *     acc = acc * x^(8 * d_len[s]) ^ d_crc[s]   over the parts in order,
+ *     d_out[m] = acc
+ * -- the identity of extend_spans (crc.cpp:393-405): for part CRCs computed
+ * from seed 0, d_out[m] = crc32c_extend / crc64ecma_extend of the
+ * concatenated bytes from seed_m (the inverted CRC-64 folds the same way).
+ * Lengths are 64-bit byte counts: a part of 4 GiB or more is one step. The
+ * definition is this linear one for arbitrary pairs: it equals a chain of
+ * crc32c_combine calls except where a part has length 0 and a non-zero CRC
+ * (the chain's len2 == 0 shortcut ignores that CRC; no real part has one),
+ * and it equals the crc64ecma_combine chain always. d_total (optional):
+ * d_total[m] = the object's byte length, wrapping mod 2^64 (the CRC is that
+ * of the definition above only while an object's lengths sum to less than
+ * 2^64). An object with no parts gives its seed and a total of 0.
+ *   - nobj == 0 returns 0 and touches nothing.
+ *   - d_crc and d_len may be null only when nparts == 0; a null d_out, or a
+ *     null d_obj_start with nobj != 1, gives -EINVAL ("null ..." in
+ *     photon_crc_last_error()).
+ * All arrays are device-accessible memory (HBM, or pinned / registered host
+ * memory read in place). Asynchronous on `stream`. The calls allocate
+ * nothing and synchronise nothing, and write only d_out[0..nobj) and
+ * d_total[0..nobj), with plain stores: no memset, no atomics, no per-stream
+ * state -- so they are capturable into a graph and replayable any number of
+ * times, also concurrently on different outputs. No CPU fallback. One
+ * workgroup folds one object, its parts spread over the workgroup's threads
+ * (64, 256 or 1,024 of them, by nparts / nobj): an object of millions of
+ * parts stays correct but runs on that one workgroup. */
+int photon_crc32c_fold_parts_n(const uint32_t* d_crc, const uint64_t* d_len,
+                               const uint64_t* d_obj_start, uint64_t nobj, uint64_t nparts,
+                               uint32_t seed0, const uint32_t* d_seeds,
+                               uint32_t* d_out, uint64_t* d_total, void* stream);
+int photon_crc64ecma_fold_parts_n(const uint64_t* d_crc, const uint64_t* d_len,
+                                  const uint64_t* d_obj_start, uint64_t nobj, uint64_t nparts,
+                                  uint64_t seed0, const uint64_t* d_seeds,
+                                  uint64_t* d_out, uint64_t* d_total, void* stream);
 
 /* Synchronous convenience: photon_crc32c_batch_strided + stream sync. */
 int photon_crc32c_batch_strided_sync(const void* d_base, uint64_t stride, uint64_t nbytes, uint64_t count,

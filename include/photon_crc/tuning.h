@@ -160,6 +160,26 @@ int photon_crc_test_tables(int which, uint32_t* out, int n);
 int photon_crc_test_long_plan(uint64_t addr, uint64_t n, int cus, int lanes, int rounds, int crc64, uint64_t* out,
                               int nout);
 
+/* CPU replay of the fold_parts kernels (photon_crc32c_fold_parts_n /
+ * photon_crc64ecma_fold_parts_n; photonlibos_amd/csrc/fold_parts.h): the
+ * kernels' per-thread run step and combine step, run on the host for a
+ * workgroup of `nthreads` threads over ONE object of `count` parts. crc[] is
+ * uint64_t words if crc64, else uint32_t; every array is host memory.
+ * *result = the object's CRC from `seed`, *total (optional) = its bytes.
+ * Returns 0, or -EINVAL. */
+int photon_crc_test_fold_parts(int crc64, const void* crc, const uint64_t* len, uint64_t count, uint64_t seed,
+                               uint32_t nthreads, uint64_t* result, uint64_t* total);
+
+/* Bench utility (scripts/bench_copy_crc.py --fold, arm (a)): the route a
+ * caller took before photon_crc32c_fold_parts_n / photon_crc64ecma_fold_parts_n
+ * existed, natively: photon_crc_stream_sync(stream), the nparts part CRCs at
+ * d_crc copied to the host, then per object acc = seed; acc =
+ * crc32c_combine / crc64ecma_combine(acc, crc[s], len[s]) over the host
+ * arrays h_len / h_obj_start (lengths below 4 GiB), h_out[m] = acc (uint32_t
+ * or, if crc64, uint64_t words). Synchronous. */
+int photon_crc_util_fold_on_host(int crc64, const void* d_crc, const uint64_t* h_len, const uint64_t* h_obj_start,
+                                 uint64_t nobj, uint64_t nparts, uint64_t seed, void* h_out, void* stream);
+
 /* Test/bench utility (not on the checksum path): fill count buffers of
  * nbytes at d_base + i*stride with the splitmix64 byte stream of seed
  * (seed_base + i), i.e. word k = mix64(seed + (k+1)*0x9E3779B97F4A7C15),

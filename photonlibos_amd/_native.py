@@ -114,6 +114,12 @@ def _declare(L):
        vp, vp, vp, vp)
     fn("photon_crc32c_copy_extend_device", ctypes.c_int, vp, vp, u64, u32, vp, vp)
     fn("photon_crc64ecma_copy_extend_device", ctypes.c_int, vp, vp, u64, u64, vp, vp)
+    fn("photon_crc64ecma_series_device", ctypes.c_int, vp, u32, u32, vp, vp)
+    fn("photon_crc64ecma_combine_series_device", ctypes.c_int, vp, u32, u32, vp, vp)
+    fn("photon_crc32c_fold_parts_n", ctypes.c_int, vp, vp, vp, u64, u64, u32, vp, vp, vp, vp)
+    fn("photon_crc64ecma_fold_parts_n", ctypes.c_int, vp, vp, vp, u64, u64, u64, vp, vp, vp, vp)
+    fn("photon_crc_test_fold_parts", ctypes.c_int, ctypes.c_int, vp, vp, u64, u64, u32, vp, vp)
+    fn("photon_crc_util_fold_on_host", ctypes.c_int, ctypes.c_int, vp, vp, vp, u64, u64, u64, vp, vp)
     # include/photon_crc/checked_batch.h
     fn("photon_crc_pinned_allocate", ctypes.c_int, vp, PhotonRange, ctypes.POINTER(vp))
     fn("photon_crc_pinned_deallocate", ctypes.c_int, vp, vp)

@@ -33,6 +33,8 @@ __all__ = [
     "copy_msg_iov_n", "copy_msg64_iov_n",
     "copy_msg_iov_seg_n", "copy_msg64_iov_seg_n", "SEG_OF_SRC", "SEG_OF_DST",
     "copy_extend_device", "copy_extend64_device",
+    "series64_device", "combine_series64_device", "fold_parts_device", "fold_parts64_device",
+    "crc64ecma_series_at", "crc64ecma_combine_series_at",
     "batch64_strided", "batch64_iov", "combine64_batch", "trim64_batch", "batch64_msg_n", "host_batch64_strided", "extend64_device", "extend_spans", "extend64_spans", "Span", "combine_batch", "fill_splitmix", "read_stream", "IOVEC_DTYPE",
 ]
 
@@ -514,6 +516,34 @@ def copy_extend64_device(src, dst, nbytes, out, seed=0, stream=None):
                                                      _ptr(out), _stream(stream)))
 
 
+def series64_device(buffer, part_size, n_parts, out, stream=None):
+    """out[i] = crc64ecma(buffer + i*part_size, part_size, 0) over device memory (uint64 out). Async."""
+    _check(lib().photon_crc64ecma_series_device(_ptr(buffer), part_size, n_parts, _ptr(out), _stream(stream)))
+
+
+def combine_series64_device(crcs, part_size, n_parts, result, stream=None):
+    """*result = crc64ecma_combine_series(crcs, part_size, n_parts) on the device (uint64). Async."""
+    _check(lib().photon_crc64ecma_combine_series_device(_ptr(crcs), part_size, n_parts, _ptr(result),
+                                                        _stream(stream)))
+
+
+def fold_parts_device(crcs, lens, obj_start, nobj, nparts, out, seed=0, seeds=None, total=None, stream=None):
+    """Fold part CRC-32Cs into object CRCs on the device: object m is the parts
+    obj_start[m]..obj_start[m+1]-1 (obj_start None: one object of all nparts), out[m] = the
+    fold acc = acc * x^(8 lens[s]) ^ crcs[s] from seeds[m] or seed; lens are uint64 byte
+    counts; total (optional, uint64) = the objects' byte lengths. Async, capturable."""
+    _check(lib().photon_crc32c_fold_parts_n(_ptr(crcs), _ptr(lens), _ptr(obj_start), nobj, nparts,
+                                            seed & 0xFFFFFFFF, _ptr(seeds), _ptr(out), _ptr(total),
+                                            _stream(stream)))
+
+
+def fold_parts64_device(crcs, lens, obj_start, nobj, nparts, out, seed=0, seeds=None, total=None, stream=None):
+    """fold_parts_device for CRC-64/ECMA (uint64 crcs / seeds / out). Async, capturable."""
+    _check(lib().photon_crc64ecma_fold_parts_n(_ptr(crcs), _ptr(lens), _ptr(obj_start), nobj, nparts,
+                                               seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(out), _ptr(total),
+                                               _stream(stream)))
+
+
 class Span(ctypes.Structure):
     """photon_crc_span (include/photon_crc/crc32c_gpu.h)."""
     _fields_ = [("device", ctypes.c_int), ("d_data", ctypes.c_void_p), ("nbytes", ctypes.c_uint64)]
@@ -543,7 +573,8 @@ def extend64_spans(spans, seed=0):
 
 
 def set_device_dispatch(on):
-    """Route crc32c_auto / crc32c_series_auto / crc32c_combine_series_auto to the
+    """Route crc32c_auto / crc32c_series_auto / crc32c_combine_series_auto and
+    crc64ecma_auto / crc64ecma_series_auto / crc64ecma_combine_series_auto to the
     device for device pointers (photon_crc_set_device_dispatch). Raises
     CrcError(-EIO) if a routed call failed on the device since the last switch
     (it was recomputed on the host: dispatch_fallbacks())."""
@@ -593,6 +624,20 @@ def crc32c_series_at(addr, part_size, n_parts, out_addr):
 def crc32c_combine_series_at(addr, part_size, n_parts):
     """crc32c_combine_series through crc32c_combine_series_auto on a raw address."""
     return _auto("crc32c_combine_series_auto", _CSER_PTR_FN)(addr, part_size, n_parts)
+
+
+_SERIES64_PTR_FN = _SERIES_PTR_FN
+_CSER64_PTR_FN = ctypes.CFUNCTYPE(ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32)
+
+
+def crc64ecma_series_at(addr, part_size, n_parts, out_addr):
+    """crc64ecma_series through crc64ecma_series_auto on raw addresses."""
+    _auto("crc64ecma_series_auto", _SERIES64_PTR_FN)(addr, part_size, n_parts, out_addr)
+
+
+def crc64ecma_combine_series_at(addr, part_size, n_parts):
+    """crc64ecma_combine_series through crc64ecma_combine_series_auto on a raw address."""
+    return _auto("crc64ecma_combine_series_auto", _CSER64_PTR_FN)(addr, part_size, n_parts)
 
 
 def host_register(addr, nbytes):

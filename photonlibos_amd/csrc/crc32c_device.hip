@@ -416,6 +416,17 @@ PowTable part_pow_table(uint64_t part) {
     return t;
 }
 
+// The same at 64 bits, for crc64_combine_series_kernel (part 0: K = 1).
+PowTable64 part_pow_table64(uint64_t part) {
+    PowTable64 t;
+    uint64_t v = xpow64(8ull * part);
+    for (int i = 0; i < 64; ++i) {
+        t.x8pow2[i] = v;
+        v = mulmod64(v, v);
+    }
+    return t;
+}
+
 // x^(-8*2^i): the right shift of crc32c_rshift_sw (crc_tables.cpp:147-164).
 const PowTable& rshift_table() {
     static PowTable t;
@@ -2226,6 +2237,125 @@ int photon_crc32c_combine_series_device(const uint32_t* d_crc, uint32_t part_siz
     return e == hipSuccess ? 0 : hip_fail(e, "combine_series kernel launch");
 }
 
+int photon_crc64ecma_series_device(const void* d_buffer, uint32_t part_size, uint32_t n_parts, uint64_t* d_crc_parts,
+                                   void* stream) {
+    if (!n_parts) return 0;
+    if (!d_crc_parts || (!d_buffer && part_size)) return fail(-EINVAL, "null buffer or output");
+    if (!part_size) {  // crc64ecma of no bytes: 0; nothing is read
+        int cus = 0;
+        int dev = current_device(&cus);
+        if (dev < 0) return dev;
+        hipError_t e = hipMemsetAsync(d_crc_parts, 0, 8ull * n_parts, static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? 0 : hip_fail(e, "hipMemsetAsync");
+    }
+    return photon_crc64ecma_batch_strided(d_buffer, part_size, part_size, n_parts, 0, nullptr, d_crc_parts, stream);
+}
+
+int photon_crc64ecma_combine_series_device(const uint64_t* d_crc, uint32_t part_size, uint32_t n_parts,
+                                           uint64_t* d_result, void* stream) {
+    if (!d_result || (!d_crc && n_parts)) return fail(-EINVAL, "null argument");
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(d_result, 0, 8, st);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+    if (!n_parts) return 0;
+    const uint64_t threads = ((uint64_t)n_parts + kSeriesChunk - 1) / kSeriesChunk;
+    hipLaunchKernelGGL(crc64_combine_series_kernel, dim3((threads + 255) / 256), dim3(256), 0, st, d_crc,
+                       (uint64_t)n_parts, d_result, part_pow_table64(part_size));
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, "crc64_combine_series_kernel launch");
+}
+
+// Workgroup size of the fold_parts kernels by parts per object (the host
+// knows the average only): a wave for up to 64, 256 threads up to 1,024,
+// 1,024 threads above.
+static uint32_t fold_parts_block_size(uint64_t nobj, uint64_t nparts) {
+    const uint64_t avg = nparts / nobj;
+    return avg <= 64 ? 64u : avg <= 1024 ? 256u : (uint32_t)kFoldMaxBlock;
+}
+
+static int fold_parts_check(const void* d_crc, const void* d_len, const void* d_obj_start, uint64_t nobj,
+                            uint64_t nparts, const void* d_out) {
+    if (!d_out) return fail(-EINVAL, "null output");
+    if ((!d_crc || !d_len) && nparts) return fail(-EINVAL, "null part CRCs or lengths");
+    if (!d_obj_start && nobj != 1) return fail(-EINVAL, "a null d_obj_start means one object: nobj must be 1");
+    return 0;
+}
+
+int photon_crc32c_fold_parts_n(const uint32_t* d_crc, const uint64_t* d_len, const uint64_t* d_obj_start,
+                               uint64_t nobj, uint64_t nparts, uint32_t seed0, const uint32_t* d_seeds,
+                               uint32_t* d_out, uint64_t* d_total, void* stream) {
+    if (!nobj) return 0;
+    if (int rc = fold_parts_check(d_crc, d_len, d_obj_start, nobj, nparts, d_out)) return rc;
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint32_t grid = nobj < kFoldMaxGrid ? (uint32_t)nobj : kFoldMaxGrid;
+    hipLaunchKernelGGL(crc32c_fold_parts_kernel, dim3(grid), dim3(fold_parts_block_size(nobj, nparts)), 0,
+                       static_cast<hipStream_t>(stream), d_crc, d_len, d_obj_start, nobj, nparts, seed0, d_seeds,
+                       d_out, d_total, pow_table());
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, "crc32c_fold_parts_kernel launch");
+}
+
+int photon_crc64ecma_fold_parts_n(const uint64_t* d_crc, const uint64_t* d_len, const uint64_t* d_obj_start,
+                                  uint64_t nobj, uint64_t nparts, uint64_t seed0, const uint64_t* d_seeds,
+                                  uint64_t* d_out, uint64_t* d_total, void* stream) {
+    if (!nobj) return 0;
+    if (int rc = fold_parts_check(d_crc, d_len, d_obj_start, nobj, nparts, d_out)) return rc;
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint32_t grid = nobj < kFoldMaxGrid ? (uint32_t)nobj : kFoldMaxGrid;
+    hipLaunchKernelGGL(crc64_fold_parts_kernel, dim3(grid), dim3(fold_parts_block_size(nobj, nparts)), 0,
+                       static_cast<hipStream_t>(stream), d_crc, d_len, d_obj_start, nobj, nparts, seed0, d_seeds,
+                       d_out, d_total, pow_table64());
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, "crc64_fold_parts_kernel launch");
+}
+
+// tuning.h, bench only: what a caller did before fold_parts_n existed.
+int photon_crc_util_fold_on_host(int crc64, const void* d_crc, const uint64_t* h_len, const uint64_t* h_obj_start,
+                                 uint64_t nobj, uint64_t nparts, uint64_t seed, void* h_out, void* stream) {
+    if (!d_crc || !h_len || !h_obj_start || !h_out) return fail(-EINVAL, "null argument");
+    if (int rc = photon_crc_stream_sync(stream)) return rc;
+    const size_t w = crc64 ? 8 : 4;
+    std::vector<uint8_t> h(nparts * w);
+    hipError_t e = hipMemcpy(h.data(), d_crc, nparts * w, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
+    for (uint64_t m = 0; m < nobj; ++m) {
+        if (crc64) {
+            const uint64_t* c = reinterpret_cast<const uint64_t*>(h.data());
+            uint64_t acc = seed;
+            for (uint64_t s = h_obj_start[m]; s < h_obj_start[m + 1]; ++s)
+                acc = crc64ecma_combine(acc, c[s], (uint32_t)h_len[s]);
+            static_cast<uint64_t*>(h_out)[m] = acc;
+        } else {
+            const uint32_t* c = reinterpret_cast<const uint32_t*>(h.data());
+            uint32_t acc = (uint32_t)seed;
+            for (uint64_t s = h_obj_start[m]; s < h_obj_start[m + 1]; ++s)
+                acc = crc32c_combine(acc, c[s], (uint32_t)h_len[s]);
+            static_cast<uint32_t*>(h_out)[m] = acc;
+        }
+    }
+    return 0;
+}
+
+// tuning.h: the kernels' per-thread and combine steps (fold_parts.h) on the host.
+int photon_crc_test_fold_parts(int crc64, const void* crc, const uint64_t* len, uint64_t count, uint64_t seed,
+                               uint32_t nthreads, uint64_t* result, uint64_t* total) {
+    if (!result || !nthreads || ((!crc || !len) && count)) return fail(-EINVAL, "null argument or no threads");
+    if (crc64)
+        *result = fold_replay<Gf64>(static_cast<const uint64_t*>(crc), len, count, seed, nthreads,
+                                    pow_table64().x8pow2, total);
+    else
+        *result = fold_replay<Gf32>(static_cast<const uint32_t*>(crc), len, count, (uint32_t)seed, nthreads,
+                                    pow_table().x8pow2, total);
+    return 0;
+}
+
 int photon_crc32c_trim_batch(const photon_crc_component* d_all, const photon_crc_component* d_prefix,
                              const photon_crc_component* d_suffix, uint64_t count, uint32_t* d_out,
                              uint32_t* d_nerr, void* stream) {
@@ -2469,6 +2599,8 @@ uint32_t (*g_host_crc)(const uint8_t*, size_t, uint32_t) = nullptr;
 uint64_t (*g_host_crc64)(const uint8_t*, size_t, uint64_t) = nullptr;
 void (*g_host_series)(const uint8_t*, uint32_t, uint32_t, uint32_t*) = nullptr;
 uint32_t (*g_host_cseries)(uint32_t*, uint32_t, uint32_t) = nullptr;
+void (*g_host_series64)(const uint8_t*, uint32_t, uint32_t, uint64_t*) = nullptr;
+uint64_t (*g_host_cseries64)(uint64_t*, uint32_t, uint32_t) = nullptr;
 
 // The saved host engines, read by the routed wrappers (written before the
 // routed pointers are published, see photon_crc_set_device_dispatch).
@@ -3347,6 +3479,65 @@ uint64_t dispatch_crc64(const uint8_t* p, size_t n, uint64_t crc) {
     return crc;
 }
 
+// dispatch_series / dispatch_combine_series for CRC-64/ECMA. The host engines
+// have no part_size quirk (crc64_cpu.cpp), so there is no engine to select.
+void dispatch_series64(const uint8_t* buf, uint32_t part, uint32_t n, uint64_t* parts) {
+    const int dev = (part && n) ? device_of(buf) : -1;
+    if (dev < 0) return host_engine(&g_host_series64)(buf, part, n, parts);
+    DeviceScope scope(dev);
+    const bool parts_on_dev = device_of(parts) == dev;
+    int rc;
+    if (parts_on_dev) {
+        RoutedStream* r = nullptr;
+        rc = routed_lease(dev, &r);
+        if (!rc) {
+            rc = photon_crc64ecma_series_device(buf, part, n, parts, r->st);
+            hipError_t e = hipStreamSynchronize(r->st);
+            if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+            routed_return(r);
+        }
+    } else {
+        rc = with_scratch(dev, 8ull * n, parts, 8ull * n, [&](void* d, hipStream_t st) {
+            return photon_crc64ecma_series_device(buf, part, n, static_cast<uint64_t*>(d), st);
+        });
+    }
+    if (!rc) return;
+    routed_failure("crc64ecma_series", rc);
+    std::vector<uint64_t> h(n);
+    uint64_t i = 0;
+    std::vector<uint8_t> part_buf;
+    for_host_chunks(buf, (size_t)part * n, "crc64ecma_series", [&](const uint8_t* hp, size_t k) {
+        // whole parts only: gather across chunk edges into part_buf
+        part_buf.insert(part_buf.end(), hp, hp + k);
+        size_t whole = part_buf.size() / part;
+        host_engine(&g_host_series64)(part_buf.data(), part, (uint32_t)whole, h.data() + i);
+        i += whole;
+        part_buf.erase(part_buf.begin(), part_buf.begin() + whole * part);
+    });
+    if (parts_on_dev) {
+        hipError_t e = hipMemcpy(parts, h.data(), 8ull * n, hipMemcpyHostToDevice);
+        if (e != hipSuccess) routed_abort("crc64ecma_series", e);
+    } else {
+        memcpy(parts, h.data(), 8ull * n);
+    }
+}
+
+uint64_t dispatch_combine_series64(uint64_t* crc, uint32_t part, uint32_t n) {
+    const int dev = n ? device_of(crc) : -1;
+    if (dev < 0) return host_engine(&g_host_cseries64)(crc, part, n);
+    DeviceScope scope(dev);
+    uint64_t r = 0;  // device scratch, as dispatch_combine_series: the kernel accumulates with device atomics
+    int rc = with_scratch(dev, 8, &r, 8, [&](void* d, hipStream_t st) {
+        return photon_crc64ecma_combine_series_device(crc, part, n, static_cast<uint64_t*>(d), st);
+    });
+    if (!rc) return r;
+    routed_failure("crc64ecma_combine_series", rc);
+    std::vector<uint64_t> h(n);
+    hipError_t e = hipMemcpy(h.data(), crc, 8ull * n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) routed_abort("crc64ecma_combine_series", e);
+    return host_engine(&g_host_cseries64)(h.data(), part, n);
+}
+
 }  // namespace
 }  // namespace pcrc
 
@@ -3369,16 +3560,24 @@ extern "C" int photon_crc_set_device_dispatch(int on) {
         __atomic_store_n(&g_host_cseries, __atomic_load_n(&crc32c_combine_series_auto, __ATOMIC_ACQUIRE),
                          __ATOMIC_RELAXED);
         __atomic_store_n(&g_host_crc64, __atomic_load_n(&crc64ecma_auto, __ATOMIC_ACQUIRE), __ATOMIC_RELAXED);
+        __atomic_store_n(&g_host_series64, __atomic_load_n(&crc64ecma_series_auto, __ATOMIC_ACQUIRE),
+                         __ATOMIC_RELAXED);
+        __atomic_store_n(&g_host_cseries64, __atomic_load_n(&crc64ecma_combine_series_auto, __ATOMIC_ACQUIRE),
+                         __ATOMIC_RELAXED);
         __atomic_store_n(&crc32c_auto, &dispatch_crc, __ATOMIC_RELEASE);
         __atomic_store_n(&crc32c_series_auto, &dispatch_series, __ATOMIC_RELEASE);
         __atomic_store_n(&crc32c_combine_series_auto, &dispatch_combine_series, __ATOMIC_RELEASE);
         __atomic_store_n(&crc64ecma_auto, &dispatch_crc64, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc64ecma_series_auto, &dispatch_series64, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc64ecma_combine_series_auto, &dispatch_combine_series64, __ATOMIC_RELEASE);
         g_dispatch_on = true;
     } else if (!on && g_dispatch_on) {
         __atomic_store_n(&crc32c_auto, g_host_crc, __ATOMIC_RELEASE);
         __atomic_store_n(&crc32c_series_auto, g_host_series, __ATOMIC_RELEASE);
         __atomic_store_n(&crc32c_combine_series_auto, g_host_cseries, __ATOMIC_RELEASE);
         __atomic_store_n(&crc64ecma_auto, g_host_crc64, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc64ecma_series_auto, g_host_series64, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc64ecma_combine_series_auto, g_host_cseries64, __ATOMIC_RELEASE);
         g_dispatch_on = false;
     }
     return g_dispatch_err.exchange(0) ? -EIO : 0;

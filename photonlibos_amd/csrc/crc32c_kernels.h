@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "../../include/photon_crc/crc32c_gpu.h"
+#include "fold_parts.h"
 #include "gf2.h"
 
 #ifndef PCRC_LANE_SEL
@@ -1621,6 +1622,84 @@ __global__ __launch_bounds__(1024) void crc32c_first_nonzero_kernel(const uint32
         __syncthreads();
     }
     if (threadIdx.x == 0) *result = first == ~0ull ? 0u : crc[first];
+}
+
+// ------------------------------------------- fold of an object's part CRCs
+// photon_crc32c_fold_parts_n / photon_crc64ecma_fold_parts_n (DESIGN.md
+// §4.8): (CRC, length) pairs from the caller, 64-bit lengths, one workgroup
+// per object (objects beyond the grid: a stride loop), the object's parts
+// spread over the workgroup's threads by fold_parts.h: thread t folds its run
+// (fold_run), the runs' byte counts are suffix-summed in LDS, each thread
+// shifts its value by the bytes behind its run (fold_shift), one thread adds
+// the seed term seed * x^(8 * total) to its value, the values are XORed over
+// the wave (DPP / shuffles) and over the waves (LDS), and thread 0 stores.
+// Plain loads and stores only; nothing but
+// out[m] and total[m] is written, so a launch is replayable and independent
+// of every other launch. The workgroup is 64, 256 or 1,024 threads (the host
+// picks by parts per object); an object of millions of parts is still one
+// workgroup's work.
+constexpr int kFoldMaxBlock = 1024;
+constexpr uint32_t kFoldMaxGrid = 4096;
+
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v) { return group_xor<64>(v); }
+__device__ __forceinline__ uint64_t wave_xor(uint64_t v) {
+    return ((uint64_t)group_xor<64>((uint32_t)(v >> 32)) << 32) | group_xor<64>((uint32_t)v);
+}
+
+template <typename G>
+__device__ __forceinline__ void fold_parts_block(const typename G::T* crc, const uint64_t* len,
+                                                 const uint64_t* obj_start, uint64_t nobj, uint64_t nparts,
+                                                 typename G::T seed0, const typename G::T* seeds,
+                                                 typename G::T* out, uint64_t* total, const typename G::T* tab) {
+    typedef typename G::T T;
+    __shared__ uint64_t behind[kFoldMaxBlock];  // suffix sums of the runs' bytes
+    __shared__ T red[kFoldMaxBlock / 64];
+    const uint32_t t = threadIdx.x, nt = blockDim.x;
+    for (uint64_t m = blockIdx.x; m < nobj; m += gridDim.x) {  // m, s0, s1, n, nact: the same on every thread
+        uint64_t s0 = obj_start ? obj_start[m] : 0ull, s1 = obj_start ? obj_start[m + 1] : nparts;
+        s1 = s1 < nparts ? s1 : nparts;  // a bad obj_start reads no part outside [0, nparts)
+        s0 = s0 < s1 ? s0 : s1;
+        const uint64_t n = s1 - s0, per = (n + nt - 1) / nt;
+        const uint32_t nact = per ? (uint32_t)((n + per - 1) / per) : 0u;  // threads with a run
+        uint64_t lo, hi;
+        fold_run_bounds(n, nt, t, &lo, &hi);
+        const FoldRun<T> r = fold_run<G>(crc + s0, len + s0, lo, hi, tab);
+        behind[t] = r.bytes;
+        __syncthreads();
+        for (uint32_t off = 1; off < nact; off <<= 1) {  // threads >= nact hold 0
+            const uint64_t v = t + off < nt ? behind[t + off] : 0ull;
+            __syncthreads();
+            behind[t] += v;
+            __syncthreads();
+        }
+        const uint64_t incl = behind[t];  // this run's bytes and every later run's
+        // The seed term (fold_finish) beside the runs, not after them: the first
+        // thread without a run shifts the seed by the total in the SAME
+        // fold_shift as the runs (lanes of a wave that call it twice would run
+        // the calls one after the other); when every thread has a run, the
+        // last thread makes a second call.
+        const T seed = seeds ? seeds[m] : seed0;
+        const bool idle = nact < nt && t == nact;
+        T v = fold_shift<G>(idle ? seed : r.acc, idle ? behind[0] : incl - r.bytes, tab);
+        if (nact == nt && t == nt - 1u) v ^= fold_shift<G>(seed, behind[0], tab);
+        const T x = wave_xor(v);
+        if ((t & 63u) == 0) red[t >> 6] = x;
+        __syncthreads();
+        if (t == 0) {
+            T all = 0;
+            for (uint32_t w = 0; w < nt / 64; ++w) all ^= red[w];
+            out[m] = all;
+            if (total) total[m] = incl;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kFoldMaxBlock) void crc32c_fold_parts_kernel(const uint32_t* crc, const uint64_t* len,
+                                                                          const uint64_t* obj_start, uint64_t nobj,
+                                                                          uint64_t nparts, uint32_t seed0,
+                                                                          const uint32_t* seeds, uint32_t* out,
+                                                                          uint64_t* total, PowTable pt) {
+    fold_parts_block<Gf32>(crc, len, obj_start, nobj, nparts, seed0, seeds, out, total, pt.x8pow2);
 }
 
 // crc32c_trim (crc.cpp:442-464) per element, including its 32-bit size sum

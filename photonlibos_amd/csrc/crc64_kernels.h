@@ -1060,6 +1060,37 @@ __global__ void crc64_msg_fold_kernel(const photon_crc_iovec* iov, const uint64_
     out[m] = acc;
 }
 
+// crc64ecma_combine_series over device memory, as crc32c_combine_series_kernel:
+// linear for every part_size (combine64's only shortcut, crc1 == 0, agrees
+// with the formula), result = XOR_i crc[i] * K^(n-1-i), K = x^(8*part_size)
+// (K = 1 for part_size 0). Thread t Horner-folds kSeriesChunk consecutive
+// parts, shifts by K^(parts after its chunk), and each wave XORs its value
+// into *result (zeroed by the caller).
+__global__ __launch_bounds__(256) void crc64_combine_series_kernel(const uint64_t* crc, uint64_t n, uint64_t* result,
+                                                                   PowTable64 kp) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t lo = t * kSeriesChunk;
+    uint64_t acc = 0;
+    if (lo < n) {
+        const uint64_t hi = lo + kSeriesChunk < n ? lo + kSeriesChunk : n;
+        for (uint64_t i = lo; i < hi; ++i) acc = (acc ? mulmod64(acc, kp.x8pow2[0]) : 0ull) ^ crc[i];
+        if (acc) acc = mulmod64(acc, xpow8_tab64(n - hi, kp));  // kp.x8pow2[j] = K^(2^j)
+    }
+    for (int off = 32; off; off >>= 1)
+        acc ^= ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(acc >> 32), off, 64) << 32) |
+               (uint32_t)__shfl_xor((int)(uint32_t)acc, off, 64);
+    if ((threadIdx.x & 63u) == 0 && acc) atomicXor((unsigned long long*)result, (unsigned long long)acc);
+}
+
+// photon_crc64ecma_fold_parts_n: fold_parts_block (crc32c_kernels.h) at 64 bits.
+__global__ __launch_bounds__(kFoldMaxBlock) void crc64_fold_parts_kernel(const uint64_t* crc, const uint64_t* len,
+                                                                         const uint64_t* obj_start, uint64_t nobj,
+                                                                         uint64_t nparts, uint64_t seed0,
+                                                                         const uint64_t* seeds, uint64_t* out,
+                                                                         uint64_t* total, PowTable64 pt) {
+    fold_parts_block<Gf64>(crc, len, obj_start, nobj, nparts, seed0, seeds, out, total, pt.x8pow2);
+}
+
 // The fold of crc64_copy_iov_seg_kernel's segment CRCs, one
 // WAVEFRONT per message (one thread per message, as crc64_msg_fold_kernel,
 // is a chain of 40 dependent loads and 16 64-step multiplies per thread for

@@ -57,12 +57,24 @@ the ratio (b)/(a), and the spread between the alternations of each arm;
                     photon_crc_memcpy_async, then extend_device over the copy (3 bytes
                     moved per payload byte); "fused" = the new call (2 bytes per payload
                     byte; floor for fused/pair ~ 0.67); "pieces" = copy_batch_strided over
-                    64 KiB pieces of the same bytes, then combine_series_device (CRC-64
-                    has no device fold: its pieces arm is the piece batch alone, the fold
-                    left to the host and not timed). "faster_3x" is true when pair - fused
+                    64 KiB pieces of the same bytes, then combine_series_device (CRC-64:
+                    combine_series64_device), both timed. "faster_3x" is true when pair - fused
                     exceeds three times the spread between pair's alternations; "within" is
                     true when |fused - pieces| is at most the larger of 3 % of pieces and
                     three times the spread of pieces. --out appends.
+  --fold : part CRCs folded into object CRCs (photon_crc32c_fold_parts_n and
+                    photon_crc64ecma_fold_parts_n, both in one run), the same alternations,
+                    one JSON line per CRC and shape (1 object x 16 parts, 1 x 10,000, 4,096 x
+                    16; parts of 1 to 16 MiB, the last of each object short): "host" = the
+                    route before the call existed, natively (photon_crc_util_fold_on_host:
+                    photon_crc_stream_sync, the part CRCs copied to the host, a loop of the
+                    host crc32c_combine / crc64ecma_combine), wall clock in us from the call
+                    to the value in hand; "device" = the new call, wall clock from the launch
+                    to the stream sync that returns d_out (pinned host memory);
+                    "device_kernel" = the launch alone by HIP events. The arms' values and
+                    the CPU replay of the kernel are compared before anything is timed.
+                    "faster_3x" is true when host - device exceeds three times the spread
+                    between host's alternations. --out appends.
 """
 import argparse
 import csv
@@ -87,6 +99,8 @@ ap.add_argument("--iov", action="store_true")
 ap.add_argument("--iov-seg", action="store_true")
 ap.add_argument("--long", action="store_true")
 ap.add_argument("--sizes", default="64,256,1024", help="--long: payload sizes in MiB")
+ap.add_argument("--fold", action="store_true")
+ap.add_argument("--tree", default="working tree", help="--fold: a label of the tree measured, written to each line")
 args = ap.parse_args()
 
 
@@ -407,6 +421,7 @@ def bench_long(mib, delta):
     def pieces():
         if args.crc64:
             ck.copy_batch64_strided(sp, piece, dp, piece, piece, count, parts, stream=st)
+            ck.combine_series64_device(parts, piece, count, out, stream=st)
         else:
             ck.copy_batch_strided(sp, piece, dp, piece, piece, count, parts, stream=st)
             ck.combine_series_device(parts, piece, count, out, stream=st)
@@ -419,10 +434,7 @@ def bench_long(mib, delta):
         torch.cuda.synchronize()
         assert torch.equal(dst[1 + delta:1 + delta + n], src[1:1 + n]), f"{name}: destination differs from the source"
         assert not bool(dst[:1 + delta].any()) and not bool(dst[1 + delta + n:].any()), f"{name}: wrote outside"
-        if name == "pieces" and args.crc64:
-            crcs[name] = ck.crc64ecma_combine_series([int(x) for x in parts.cpu().numpy().view(np.uint64)], piece)
-        else:
-            crcs[name] = int(out.cpu().numpy().view(np.uint64 if args.crc64 else np.uint32)[0])
+        crcs[name] = int(out.cpu().numpy().view(np.uint64 if args.crc64 else np.uint32)[0])
     assert crcs["pair"] == crcs["fused"] == crcs["pieces"], f"the arms' CRCs differ: {crcs}"
     means = {k: [] for k in arms}
     times = {k: [] for k in arms}
@@ -443,7 +455,7 @@ def bench_long(mib, delta):
     gib = n / 2.0**30
     res = {"shape": "long", "crc": "crc64ecma" if args.crc64 else "crc32c", "MiB": mib, "src": "buf+1",
            "dst": f"dbuf+{1 + delta}", "co_aligned": delta % 16 == 0, "piece_bytes": piece,
-           "pieces_fold": "host, not timed" if args.crc64 else "combine_series_device", "rounds": args.rounds,
+           "pieces_fold": "combine_series64_device" if args.crc64 else "combine_series_device", "rounds": args.rounds,
            "reps": args.reps, "warmup": args.warmup}
     for name in arms:
         ms = np.asarray(times[name])
@@ -461,6 +473,99 @@ def bench_long(mib, delta):
     res["fused_slower_than_pieces"] = bool(b - c > res["allowed_ms"])
     return res
 
+
+FOLD_SHAPES = [(1, 16), (1, 10000), (4096, 16)]  # objects x parts per object
+
+
+def bench_fold(crc64, nobj, per):
+    import time
+    rng = np.random.default_rng(0xF01D + nobj + per)
+    nparts = nobj * per
+    wdt = np.uint64 if crc64 else np.uint32
+    lens = rng.integers(1 << 20, 1 << 24, nparts).astype(np.uint64)  # unequal parts of 1 to 16 MiB ...
+    lens[per - 1::per] = rng.integers(1, 1 << 20, nobj)              # ... and a short last part
+    crcs = rng.integers(0, 1 << 63, nparts, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    crcs = crcs if crc64 else (crcs >> np.uint64(32)).astype(np.uint32)
+    start = np.arange(nobj + 1, dtype=np.uint64) * np.uint64(per)
+    seed = 0xFEDCBA9876543210 if crc64 else 0x9E3779B1
+    d_crc = torch.from_numpy(crcs.view(np.int64 if crc64 else np.int32)).cuda()
+    d_len = torch.from_numpy(lens.view(np.int64)).cuda()
+    d_start = torch.from_numpy(start.view(np.int64)).cuda()
+    out_b = torch.zeros(nobj, dtype=torch.int64 if crc64 else torch.int32).pin_memory()  # in hand after the sync
+    out_a = np.zeros(nobj, wdt)
+    fold = ck.fold_parts64_device if crc64 else ck.fold_parts_device
+    sh = st.cuda_stream
+
+    def host():    # (a): sync, part CRCs to the host, a loop of the library's host combine
+        ck._check(lib().photon_crc_util_fold_on_host(int(crc64), d_crc.data_ptr(), lens.ctypes.data,
+                                                     start.ctypes.data, nobj, nparts, seed, out_a.ctypes.data, sh))
+
+    def launch():
+        fold(d_crc, d_len, d_start, nobj, nparts, out_b, seed=seed, stream=st)
+
+    def device():  # (b): the launch, then the stream sync that returns d_out
+        launch()
+        ck._check(lib().photon_crc_stream_sync(sh))
+
+    torch.cuda.synchronize()
+    host()
+    device()
+    got = out_b.numpy().view(wdt)
+    assert np.array_equal(out_a, got), f"the arms' values differ: {out_a[:4]} {got[:4]}"
+    import ctypes
+    res0, nt = ctypes.c_uint64(0), 64 if per <= 64 else 256 if per <= 1024 else 1024
+    ck._check(lib().photon_crc_test_fold_parts(int(crc64), crcs.ctypes.data, lens.ctypes.data, per, seed, nt,
+                                               ctypes.addressof(res0), None))
+    assert res0.value == int(got[0]), "the device fold differs from its CPU replay"
+    arms = {"host": host, "device": device}
+    times = {"host": [], "device": [], "device_kernel": []}
+    means = {k: [] for k in times}
+    for r in range(args.rounds):
+        for name in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+            fn = arms[name]
+            for _ in range(args.warmup):
+                fn()
+            t = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e6)
+            times[name] += t
+            means[name].append(float(np.mean(t)))
+            if name == "device":  # the kernel alone, by events on the launch stream
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.reps + 1)]
+                ev[0].record(st)
+                for k in range(args.reps):
+                    launch()
+                    ev[k + 1].record(st)
+                torch.cuda.synchronize()
+                t = [ev[k].elapsed_time(ev[k + 1]) * 1e3 for k in range(args.reps)]
+                times["device_kernel"] += t
+                means["device_kernel"].append(float(np.mean(t)))
+    res = {"shape": "fold", "crc": "crc64ecma" if crc64 else "crc32c", "objects": nobj, "parts_per_object": per,
+           "workgroup_threads": nt, "tree": args.tree, "rounds": args.rounds, "reps": args.reps,
+           "warmup": args.warmup}
+    for name in times:
+        us = np.asarray(times[name])
+        res[name] = {"us_mean": round(float(us.mean()), 3), "us_median": round(float(np.median(us)), 3),
+                     "round_means_us": [round(m, 3) for m in means[name]],
+                     "spread_us": round(max(means[name]) - min(means[name]), 3)}
+    a, b = res["host"]["us_mean"], res["device"]["us_mean"]
+    res["ratio_device_over_host"] = round(b / a, 4)
+    res["margin_over_host_spread"] = round((a - b) / max(res["host"]["spread_us"], 1e-9), 2)
+    res["faster_3x"] = bool(a - b > 3 * res["host"]["spread_us"])
+    return res
+
+
+if args.fold:
+    for c64 in (False, True):
+        for nobj, per in FOLD_SHAPES:
+            line = json.dumps(bench_fold(c64, nobj, per))
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+    sys.exit(0)
 
 if args.long:
     sizes = [int(x) for x in args.sizes.split(",")]
