@@ -49,6 +49,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <photon/common/checksum/crc32c.h>
@@ -156,8 +157,10 @@ int fail(int code, const std::string& what) {
     return code;
 }
 
-int hip_fail(hipError_t e, const char* what) {
-    return fail(-EIO, std::string(what) + ": " + hipGetErrorString(e));
+// what + rest: a kernel's name prefix (Crc32c::kKernel, Crc64::kKernel) and
+// the rest of the text, joined only when there is an error to report.
+int hip_fail(hipError_t e, const char* what, const char* rest = "") {
+    return fail(-EIO, std::string(what) + rest + ": " + hipGetErrorString(e));
 }
 
 // The device runtime of multi_device.h.
@@ -366,79 +369,59 @@ const LaneConsts& lane_consts(int g, int b = 1) {
     return tab[lg][lb];
 }
 
-const PowTable& pow_table() {
-    static PowTable t;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        uint32_t v = xpow(8);  // x^8
-        for (int i = 0; i < 64; ++i) {
-            t.x8pow2[i] = v;
-            v = mulmod(v, v);
-        }
-    });
-    return t;
+LaneConsts64 make_lane_consts64(int g) {
+    LaneConsts64 c;
+    c.kshift = xpow64(8ull * 16ull * (uint64_t)g);
+    for (int i = 0; i < 64; ++i) c.sbasis[i] = mulmod64(1ull << i, c.kshift);
+    return c;
 }
 
-const PowTable64& pow_table64() {
-    static PowTable64 t;
+const LaneConsts64& lane_consts64(int g) {
+    static LaneConsts64 tab[7];
     static std::once_flag once;
     std::call_once(once, [] {
-        uint64_t v = xpow64(8);
-        for (int i = 0; i < 64; ++i) {
-            t.x8pow2[i] = v;
-            v = mulmod64(v, v);
-        }
+        for (int lg = 2; lg <= 6; ++lg) tab[lg] = make_lane_consts64(1 << lg);
     });
-    return t;
+    return tab[g == 64 ? 6 : g == 32 ? 5 : g == 16 ? 4 : g == 8 ? 3 : 2];
 }
 
-const PowTable64& rshift_table64() {
-    static PowTable64 t;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        uint64_t v = xpow64_inv(8);
-        for (int i = 0; i < 64; ++i) {
-            t.x8pow2[i] = v;
-            v = mulmod64(v, v);
-        }
-    });
-    return t;
-}
-
-// x^(8*part*2^i): powers of K = x^(8*part) for the combine_series kernel.
-PowTable part_pow_table(uint64_t part) {
-    PowTable t;
-    uint32_t v = xpow(8ull * part);
+// The power tables of width W (Crc32c or Crc64, below): t[i] = v^(2^i), 64
+// successive squarings of v.
+template <typename W>
+typename W::Pow squarings(typename W::T v) {
+    typename W::Pow t;
     for (int i = 0; i < 64; ++i) {
         t.x8pow2[i] = v;
-        v = mulmod(v, v);
+        v = W::mul(v, v);
     }
     return t;
 }
 
-// The same at 64 bits, for crc64_combine_series_kernel (part 0: K = 1).
-PowTable64 part_pow_table64(uint64_t part) {
-    PowTable64 t;
-    uint64_t v = xpow64(8ull * part);
-    for (int i = 0; i < 64; ++i) {
-        t.x8pow2[i] = v;
-        v = mulmod64(v, v);
-    }
+// x^(8*2^i), or with INV x^(-8*2^i), built once.
+template <typename W, bool INV>
+const typename W::Pow& x8_table() {
+    static typename W::Pow t;
+    static std::once_flag once;
+    std::call_once(once, [] { t = squarings<W>(INV ? W::xpow_inv(8) : W::xpow(8)); });
     return t;
+}
+
+template <typename W>
+const typename W::Pow& pow_table() {
+    return x8_table<W, false>();
 }
 
 // x^(-8*2^i): the right shift of crc32c_rshift_sw (crc_tables.cpp:147-164).
-const PowTable& rshift_table() {
-    static PowTable t;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        uint32_t v = xpow_inv(8);
-        for (int i = 0; i < 64; ++i) {
-            t.x8pow2[i] = v;
-            v = mulmod(v, v);
-        }
-    });
-    return t;
+template <typename W>
+const typename W::Pow& rshift_table() {
+    return x8_table<W, true>();
+}
+
+// x^(8*part*2^i): powers of K = x^(8*part) for the combine_series kernels
+// (CRC-64 with part 0: K = 1).
+template <typename W>
+typename W::Pow part_pow_table(uint64_t part) {
+    return squarings<W>(W::xpow(8ull * part));
 }
 
 // Lanes per buffer: one wavefront per buffer for large buffers; pack small
@@ -462,49 +445,223 @@ int batch_lanes(uint64_t typical_len) {
     return choose_lanes(typical_len);
 }
 
+// The default rows per step of a lane-group size.
+constexpr int default_rows(int g) { return g == 16 ? 2 : 4; }
+
 int batch_rows(int g) {
     const int u = g_generic_u.load(std::memory_order_relaxed);
-    return u >= 0 ? u : g == 16 ? 2 : 4;
+    return u >= 0 ? u : default_rows(g);
 }
 
+std::vector<uint32_t> small_image_host();    // (below) the small kernels' table images
+std::vector<uint64_t> small64_image_host();
 
-// lanes: 0 = by typical_len (batch_lanes), else the lane-group size.
-int launch_batch(const BatchArgs& a, uint64_t typical_len, hipStream_t stream, int lanes = 0) {
-    if (a.count == 0) return 0;
+// The two CRC widths. The host paths below are written once, as templates over
+// one of these structs; whatever differs between CRC-32C and CRC-64/ECMA on
+// the host side is a member here (or a pair of overloads on the kernels'
+// argument structs, for the launchers), never a branch inside a shared body.
+// Gf32 / Gf64 (fold_parts.h) give the word type T and mul() = mulmod.
+struct Crc32c : Gf32 {
+    static constexpr const char* kKernel = "crc32c";  // the kernels' name prefix, for error texts
+    static constexpr const char* kExtend = "crc32c_extend";  // the drop-in calls, for routed failures
+    static constexpr const char* kSeries = "crc32c_series";
+    static constexpr const char* kCombineSeries = "crc32c_combine_series";
+    static constexpr const char* kCombineSeriesLaunch = "combine_series kernel launch";
+    static constexpr bool kCrc64 = false;  // long_plan_for / long_powers
+    static constexpr int kService = 0;     // service_small's kind
+    typedef LaneConsts Lanes;
+    typedef PowTable Pow;
+    typedef BatchArgs Batch;
+    typedef CopyBatchArgs CopyBatch;
+    typedef CopyIovArgs CopyIov;
+    typedef SmallArgs Small;
+    typedef LongArgs Long;
+    typedef CopyLongArgs CopyLong;
+    static T xpow(uint64_t n) { return pcrc::xpow(n); }
+    static T xpow_inv(uint64_t n) { return pcrc::xpow_inv(n); }
+    static const Lanes& lanes(int g) { return lane_consts(g); }
+    // Uniform aligned batches start from seed0 * x^(8 nbytes) (crc32c_kernels.h shift_init).
+    static constexpr bool kShiftInit = PCRC_SHIFT_INIT;
+    static T shift_init(T seed0, uint64_t nbytes) { return mul(seed0, xpow(8ull * nbytes)); }
+    // Strided and iovec copies take the lanes of the plain batch (batch_lanes:
+    // 16 lanes for 4-8 KiB).
+    static int copy_lanes(uint64_t typical_len) { return batch_lanes(typical_len); }
+    // crc32c_series_hw (crc.cpp:481-500) leaves parts below 8 bytes at 0.
+    static constexpr uint32_t kSeriesMinPart = 8;
+    // The small kernel: the seed's 4 bytes lie inside the grid; stored as given.
+    static constexpr uint32_t kSeedBytes = 4;
+    static void put_seed(Small* a, T seed) { a->seed = seed; }
+    static T seed_word(const Small& a) { return a.seed; }
+    static constexpr uint32_t kImageBytes = kSmImage;
+    static constexpr const char* kImageName = "small-buffer table image";
+    static std::vector<T> image_host() { return small_image_host(); }
+    static constexpr uint32_t kMidBlocks = pcrc::kMidBlocks, kMidRows = pcrc::kMidRows;
+    template <uint32_t V, int R>
+    static auto small_kernel() { return &crc32c_small_kernel<V, R>; }
+    template <int G>
+    static auto long_kernel() { return &crc32c_long_kernel<G, 4>; }
+    template <int G>
+    static auto copy_long_kernel() { return &crc32c_copy_long_kernel<G, 4>; }
+    static void long_args(Long* a, const LongPlan& lp, const LongPowers& pw, const void* data, T seed, T* out) {
+        pcrc::long_args(a, lp, pw, data, seed, out);
+    }
+    static constexpr auto* kCombineKernel = &crc32c_combine_kernel;
+    static constexpr auto* kTrimKernel = &crc32c_trim_kernel;
+    static constexpr auto* kFoldPartsKernel = &crc32c_fold_parts_kernel;
+    static constexpr auto* kCombineSeriesKernel = &crc32c_combine_series_kernel;
+    // combine_series over empty parts: crc32c_combine_series_hw/sw return the
+    // first nonzero part CRC (a kernel of its own). true = launched.
+    static bool combine_series_of_empty(const T* d_crc, uint32_t part_size, uint32_t n_parts, T* d_result,
+                                        hipStream_t st) {
+        if (part_size) return false;
+        hipLaunchKernelGGL(crc32c_first_nonzero_kernel, dim3(1), dim3(1024), 0, st, d_crc, (uint64_t)n_parts,
+                           d_result);
+        return true;
+    }
+    // A routed result: one tagged word per workgroup (small kernel) or one in
+    // all (long_reduce), the CRC in its low half.
+    static constexpr uint32_t kWords = 1;
+    static T routed_result(const uint32_t* x, bool /*raw*/) { return x[0]; }
+    static void routed_diag(char* buf, size_t n, const volatile uint64_t* w, uint32_t tag) {
+        snprintf(buf, n, "; word %016llx, tag %08x", (unsigned long long)w[0], tag);
+    }
+    // The host engines saved from the drop-in pointers (written before the
+    // routed pointers are published, see photon_crc_set_device_dispatch).
+    static inline T (*host_crc)(const uint8_t*, size_t, T) = nullptr;
+    static inline void (*host_series)(const uint8_t*, uint32_t, uint32_t, T*) = nullptr;
+    static inline T (*host_cseries)(T*, uint32_t, uint32_t) = nullptr;
+};
+
+struct Crc64 : Gf64 {
+    static constexpr const char* kKernel = "crc64";
+    static constexpr const char* kExtend = "crc64ecma_extend";
+    static constexpr const char* kSeries = "crc64ecma_series";
+    static constexpr const char* kCombineSeries = "crc64ecma_combine_series";
+    static constexpr const char* kCombineSeriesLaunch = "crc64_combine_series_kernel launch";
+    static constexpr bool kCrc64 = true;
+    static constexpr int kService = 1;
+    typedef LaneConsts64 Lanes;
+    typedef PowTable64 Pow;
+    typedef Batch64Args Batch;
+    typedef CopyBatch64Args CopyBatch;
+    typedef CopyIov64Args CopyIov;
+    typedef Small64Args Small;
+    typedef Long64Args Long;
+    typedef CopyLong64Args CopyLong;
+    static T xpow(uint64_t n) { return xpow64(n); }
+    static T xpow_inv(uint64_t n) { return xpow64_inv(n); }
+    static const Lanes& lanes(int g) { return lane_consts64(g); }
+    // The register starts from the inverted seed (crc.cpp:119-122).
+    static constexpr bool kShiftInit = PCRC64_SHIFT_INIT;
+    static T shift_init(T seed0, uint64_t nbytes) { return mul(~seed0, xpow(8ull * nbytes)); }
+    // Strided and iovec copies take choose_lanes as it is, without the 4-8 KiB
+    // rule of the plain batch.
+    static int copy_lanes(uint64_t typical_len) { return choose_lanes(typical_len); }
+    // crc64ecma of no bytes is 0; every other part size is read (the host
+    // engines have no short-part rule, crc64_cpu.cpp).
+    static constexpr uint32_t kSeriesMinPart = 1;
+    // The small kernel: the init's 8 bytes lie inside the grid; stored inverted.
+    static constexpr uint32_t kSeedBytes = 8;
+    static void put_seed(Small* a, T seed) { a->init = ~seed; }
+    static T seed_word(const Small& a) { return a.init; }
+    static constexpr uint32_t kImageBytes = kSm64Image;
+    static constexpr const char* kImageName = "CRC-64 small-buffer table image";
+    static std::vector<T> image_host() { return small64_image_host(); }
+    static constexpr uint32_t kMidBlocks = kMid64Blocks, kMidRows = kMid64Rows;
+    template <uint32_t V, int R>
+    static auto small_kernel() { return &crc64_small_kernel<V, R>; }
+    template <int G>
+    static auto long_kernel() { return &crc64_long_kernel<G>; }
+    template <int G>
+    static auto copy_long_kernel() { return &crc64_copy_long_kernel<G>; }
+    static void long_args(Long* a, const LongPlan& lp, const LongPowers& pw, const void* data, T seed, T* out) {
+        long_args64(a, lp, pw, data, seed, out);
+    }
+    static constexpr auto* kCombineKernel = &crc64_combine_kernel;
+    static constexpr auto* kTrimKernel = &crc64_trim_kernel;
+    static constexpr auto* kFoldPartsKernel = &crc64_fold_parts_kernel;
+    static constexpr auto* kCombineSeriesKernel = &crc64_combine_series_kernel;
+    // No rule for empty parts: K = x^0 = 1 in crc64_combine_series_kernel.
+    static bool combine_series_of_empty(const T*, uint32_t, uint32_t, T*, hipStream_t) { return false; }
+    // A routed result: two tagged words, low and high half. The small kernel's
+    // workgroups return raw values, which the host XORs and inverts
+    // (crc.cpp:119-122); long_reduce has inverted its result already.
+    static constexpr uint32_t kWords = 2;
+    static T routed_result(const uint32_t* x, bool raw) {
+        const T v = ((T)x[1] << 32) | x[0];
+        return raw ? ~v : v;
+    }
+    static void routed_diag(char* buf, size_t n, const volatile uint64_t* w, uint32_t tag) {
+        snprintf(buf, n, "; words %016llx %016llx, tag %08x", (unsigned long long)w[0], (unsigned long long)w[1],
+                 tag);
+    }
+    static inline T (*host_crc)(const uint8_t*, size_t, T) = nullptr;
+    static inline void (*host_series)(const uint8_t*, uint32_t, uint32_t, T*) = nullptr;
+    static inline T (*host_cseries)(T*, uint32_t, uint32_t) = nullptr;
+};
+
+// The persistent grid of a batch launch: `units` buffers or messages, 64 / g
+// of them per wavefront, kWaves wavefronts per workgroup, at most one
+// workgroup per CU and, when `capped`, at most photon_crc_set_batch_grid's.
+uint64_t batch_grid(uint64_t units, int g, int cus, bool capped) {
+    const uint64_t gpw = 64 / (uint64_t)g;
+    const uint64_t waves = (units + gpw - 1) / gpw;
+    uint64_t grid = (waves + kWaves - 1) / kWaves;
+    if (grid > (uint64_t)cus) grid = cus;
+    if (capped)
+        if (const int cap = g_grid_cap.load(std::memory_order_relaxed))
+            grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
+    return grid;
+}
+
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// The lane-group size as a compile-time constant: f(Int<G>{}).
+template <typename F>
+void with_lanes(int g, F f) {
+    switch (g) {
+        case 64: f(Int<64>{}); break;
+        case 32: f(Int<32>{}); break;
+        case 16: f(Int<16>{}); break;
+        case 8: f(Int<8>{}); break;
+        default: f(Int<4>{}); break;
+    }
+}
+
+// One persistent launch over `units` buffers or messages in groups of g
+// lanes: launch(Int<G>{}, grid, kc) enqueues the kernel build of G lanes.
+template <typename W, typename L>
+int launch_lanes(uint64_t units, int g, bool capped, hipStream_t stream, const char* what, L launch) {
+    if (units == 0) return 0;
     int cus = 0;
     int dev = current_device(&cus);
     if (dev < 0) return dev;
-    const int g = lanes ? lanes : batch_lanes(typical_len);
-    const uint64_t gpw = 64 / g;
-    const uint64_t waves = (a.count + gpw - 1) / gpw;
-    uint64_t grid = (waves + kWaves - 1) / kWaves;
-    if (grid > (uint64_t)cus) grid = cus;
-    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
-    const int rows_per_step = batch_rows(g);
-    const LaneConsts& kc = lane_consts(g);
+    const dim3 grid(batch_grid(units, g, cus, capped));
+    const typename W::Lanes& kc = W::lanes(g);
     HeavyLaunch heavy(stream);
-#define LB(GG, UU) \
-    hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU>), dim3(grid), dim3(kBlock), 0, stream, a, kc, pow_table())
-#define LBG(UU)                    \
-    switch (g) {                   \
-        case 64: LB(64, UU); break; \
-        case 32: LB(32, UU); break; \
-        case 16: LB(16, UU); break; \
-        case 8: LB(8, UU); break;   \
-        default: LB(4, UU); break;  \
-    }
-    if (rows_per_step == 2) {
-        LBG(2)
-    } else if (rows_per_step == 8) {
-        LBG(8)
-    } else {
-        LBG(4)
-    }
-#undef LBG
-#undef LB
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "crc32c_batch_kernel launch");
-    return 0;
+    with_lanes(g, [&](auto G) { launch(G, grid, kc); });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, what);
+}
+
+// lanes: 0 = by typical_len (batch_lanes), else the lane-group size.
+int launch_batch(const BatchArgs& a, uint64_t typical_len, hipStream_t stream, int lanes = 0) {
+    const int g = lanes ? lanes : batch_lanes(typical_len);
+    const int rows_per_step = batch_rows(g);
+    return launch_lanes<Crc32c>(a.count, g, true, stream, "crc32c_batch_kernel launch",
+                                [&](auto G, dim3 grid, const LaneConsts& kc) {
+        auto rows = [&](auto U) {
+            hipLaunchKernelGGL((crc32c_batch_kernel<decltype(G)::value, decltype(U)::value>), grid, dim3(kBlock), 0,
+                               stream, a, kc, pow_table<Crc32c>());
+        };
+        if (rows_per_step == 2)
+            rows(Int<2>{});
+        else if (rows_per_step == 8)
+            rows(Int<8>{});
+        else
+            rows(Int<4>{});
+    });
 }
 
 // The copying kernels (crc32c_batch_kernel<G, U, MSG, true>): one build per
@@ -512,128 +669,51 @@ int launch_batch(const BatchArgs& a, uint64_t typical_len, hipStream_t stream, i
 // (photon_crc_set_generic_rows does not apply; photon_crc_set_lanes_per_buffer
 // does). msg: 0 = buffers, 1 = messages chained, 2 = messages with per-segment
 // CRCs; units = buffers or messages.
-int launch_copy(const CopyBatchArgs& a, int msg, uint64_t units, int g, hipStream_t stream) {
-    if (units == 0) return 0;
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    const uint64_t gpw = 64 / g;
-    const uint64_t waves = (units + gpw - 1) / gpw;
-    uint64_t grid = (waves + kWaves - 1) / kWaves;
-    if (grid > (uint64_t)cus) grid = cus;
-    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
-    const LaneConsts& kc = lane_consts(g);
-    HeavyLaunch heavy(stream);
-#define LC(GG, UU)                                                                                                     \
-    do {                                                                                                               \
-        if (msg == 2)                                                                                                  \
-            hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU, 2, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc,     \
-                               pow_table());                                                                           \
-        else if (msg == 1)                                                                                             \
-            hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU, 1, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc,     \
-                               pow_table());                                                                           \
-        else                                                                                                           \
-            hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU, 0, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc,     \
-                               pow_table());                                                                           \
-    } while (0)
-    switch (g) {
-        case 64: LC(64, 4); break;
-        case 32: LC(32, 4); break;
-        case 16: LC(16, 2); break;
-        case 8: LC(8, 4); break;
-        default: LC(4, 4); break;
-    }
-#undef LC
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "crc32c_batch_kernel<copy> launch");
-    return 0;
+int launch_copy(const CopyBatchArgs& a, uint64_t units, int g, hipStream_t stream, int msg = 0) {
+    return launch_lanes<Crc32c>(units, g, true, stream, "crc32c_batch_kernel<copy> launch",
+                                [&](auto G, dim3 grid, const LaneConsts& kc) {
+        constexpr int GG = decltype(G)::value, U = default_rows(GG);
+        if (msg == 2)
+            hipLaunchKernelGGL((crc32c_batch_kernel<GG, U, 2, true>), grid, dim3(kBlock), 0, stream, a, kc,
+                               pow_table<Crc32c>());
+        else if (msg == 1)
+            hipLaunchKernelGGL((crc32c_batch_kernel<GG, U, 1, true>), grid, dim3(kBlock), 0, stream, a, kc,
+                               pow_table<Crc32c>());
+        else
+            hipLaunchKernelGGL((crc32c_batch_kernel<GG, U, 0, true>), grid, dim3(kBlock), 0, stream, a, kc,
+                               pow_table<Crc32c>());
+    });
 }
 
 // crc32c_copy_iov_kernel<G, U>: one build per lane-group
 // size with the default rows per step of that size, grid as launch_copy.
 int launch_copy_iov(const CopyIovArgs& a, int g, hipStream_t stream) {
-    if (a.nmsg == 0) return 0;
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    const uint64_t gpw = 64 / g;
-    const uint64_t waves = (a.nmsg + gpw - 1) / gpw;
-    uint64_t grid = (waves + kWaves - 1) / kWaves;
-    if (grid > (uint64_t)cus) grid = cus;
-    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
-    const LaneConsts& kc = lane_consts(g);
-    HeavyLaunch heavy(stream);
-#define LCI(GG, UU) hipLaunchKernelGGL((crc32c_copy_iov_kernel<GG, UU>), dim3(grid), dim3(kBlock), 0, stream, a, kc)
-    switch (g) {
-        case 64: LCI(64, 4); break;
-        case 32: LCI(32, 4); break;
-        case 16: LCI(16, 2); break;
-        case 8: LCI(8, 4); break;
-        default: LCI(4, 4); break;
-    }
-#undef LCI
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "crc32c_copy_iov_kernel launch");
-    return 0;
+    return launch_lanes<Crc32c>(a.nmsg, g, true, stream, "crc32c_copy_iov_kernel launch",
+                                [&](auto G, dim3 grid, const LaneConsts& kc) {
+        constexpr int GG = decltype(G)::value;
+        hipLaunchKernelGGL((crc32c_copy_iov_kernel<GG, default_rows(GG)>), grid, dim3(kBlock), 0, stream, a, kc);
+    });
 }
 
 // crc32c_copy_iov_seg_kernel<G, U, DST>: as launch_copy_iov,
 // one build per lane-group size and side.
 int launch_copy_iov_seg(const CopyIovSegArgs& a, bool dst_side, int g, hipStream_t stream) {
-    if (a.nmsg == 0) return 0;
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    const uint64_t gpw = 64 / g;
-    const uint64_t waves = (a.nmsg + gpw - 1) / gpw;
-    uint64_t grid = (waves + kWaves - 1) / kWaves;
-    if (grid > (uint64_t)cus) grid = cus;
-    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
-    const LaneConsts& kc = lane_consts(g);
-    HeavyLaunch heavy(stream);
-#define LCS(GG, UU)                                                                                                  \
-    do {                                                                                                             \
-        if (dst_side)                                                                                                \
-            hipLaunchKernelGGL((crc32c_copy_iov_seg_kernel<GG, UU, true>), dim3(grid), dim3(kBlock), 0, stream, a,   \
-                               kc, pow_table());                                                                     \
-        else                                                                                                         \
-            hipLaunchKernelGGL((crc32c_copy_iov_seg_kernel<GG, UU, false>), dim3(grid), dim3(kBlock), 0, stream, a,  \
-                               kc, pow_table());                                                                     \
-    } while (0)
-    switch (g) {
-        case 64: LCS(64, 4); break;
-        case 32: LCS(32, 4); break;
-        case 16: LCS(16, 2); break;
-        case 8: LCS(8, 4); break;
-        default: LCS(4, 4); break;
-    }
-#undef LCS
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "crc32c_copy_iov_seg_kernel launch");
-    return 0;
-}
-
-LaneConsts64 make_lane_consts64(int g) {
-    LaneConsts64 c;
-    c.kshift = xpow64(8ull * 16ull * (uint64_t)g);
-    for (int i = 0; i < 64; ++i) c.sbasis[i] = mulmod64(1ull << i, c.kshift);
-    return c;
-}
-
-const LaneConsts64& lane_consts64(int g) {
-    static LaneConsts64 tab[7];
-    static std::once_flag once;
-    std::call_once(once, [] {
-        for (int lg = 2; lg <= 6; ++lg) tab[lg] = make_lane_consts64(1 << lg);
+    return launch_lanes<Crc32c>(a.nmsg, g, true, stream, "crc32c_copy_iov_seg_kernel launch",
+                                [&](auto G, dim3 grid, const LaneConsts& kc) {
+        constexpr int GG = decltype(G)::value, U = default_rows(GG);
+        if (dst_side)
+            hipLaunchKernelGGL((crc32c_copy_iov_seg_kernel<GG, U, true>), grid, dim3(kBlock), 0, stream, a, kc,
+                               pow_table<Crc32c>());
+        else
+            hipLaunchKernelGGL((crc32c_copy_iov_seg_kernel<GG, U, false>), grid, dim3(kBlock), 0, stream, a, kc,
+                               pow_table<Crc32c>());
     });
-    return tab[g == 64 ? 6 : g == 32 ? 5 : g == 16 ? 4 : g == 8 ? 3 : 2];
 }
 
-int launch_batch64(const Batch64Args& a, uint64_t typical_len, hipStream_t stream) {
-    if (a.count == 0) return 0;
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
+// The CRC-64 plain batch. Unlike launch_batch above it picks its lanes with
+// choose_lanes and the 4-8 KiB rule below, takes the full-row kernel for
+// whole-step uniform batches (g_full64), and has no rows knob.
+int launch_batch(const Batch64Args& a, uint64_t typical_len, hipStream_t stream) {
     int g = choose_lanes(typical_len);
     const uint32_t full = g_full64.load(std::memory_order_relaxed);
     // rows per step: automatic mode 4 rows for buffers of 8 KiB and more (8
@@ -654,163 +734,89 @@ int launch_batch64(const Batch64Args& a, uint64_t typical_len, hipStream_t strea
     // repo:profiles/r04_ab_crc64_c3_lanes8_vs_16.jsonl).
     if (!g_lanes_override.load(std::memory_order_relaxed) && typical_len >= 4096 && typical_len <= 8192)
         g = full_rows(8) ? 8 : 16;
-    const uint64_t gpw = 64 / g;
-    const uint64_t waves = (a.count + gpw - 1) / gpw;
-    uint64_t grid = (waves + kWaves - 1) / kWaves;
-    if (grid > (uint64_t)cus) grid = cus;
-    const LaneConsts64& kc = lane_consts64(g);
-    HeavyLaunch heavy(stream);
     // Whole-step uniform batches: the full-row kernel (crc64_kernels.h).
-    if (const int fx = full_rows(g)) {
-#define LF64(GG, UU)                                                                                          \
-    do {                                                                                                      \
-        if (fx == 2)                                                                                          \
-            hipLaunchKernelGGL((crc64_full_kernel<GG, UU, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc);  \
-        else                                                                                                  \
-            hipLaunchKernelGGL((crc64_full_kernel<GG, UU, false>), dim3(grid), dim3(kBlock), 0, stream, a, kc); \
-    } while (0)
-#define LF64G(UU)                     \
-    switch (g) {                      \
-        case 64: LF64(64, UU); break; \
-        case 32: LF64(32, UU); break; \
-        case 16: LF64(16, UU); break; \
-        case 8: LF64(8, UU); break;   \
-        default: LF64(4, UU); break;  \
-    }
-        if (fu == 4) {
-            LF64G(4)
-        } else {
-            LF64G(2)
-        }
-#undef LF64G
-#undef LF64
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "crc64_full_kernel launch");
-    }
-    switch (g) {
-        case 64: hipLaunchKernelGGL(crc64_batch_kernel<64>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
-        case 32: hipLaunchKernelGGL(crc64_batch_kernel<32>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
-        case 16: hipLaunchKernelGGL(crc64_batch_kernel<16>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
-        case 8: hipLaunchKernelGGL(crc64_batch_kernel<8>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
-        default: hipLaunchKernelGGL(crc64_batch_kernel<4>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "crc64_batch_kernel launch");
-    return 0;
+    const int fx = full_rows(g);
+    // capped = false: photon_crc_set_batch_grid does not apply to the plain
+    // CRC-64 batch (this launcher "is as it was").
+    return launch_lanes<Crc64>(a.count, g, false, stream, fx ? "crc64_full_kernel launch" : "crc64_batch_kernel launch",
+                               [&](auto G, dim3 grid, const LaneConsts64& kc) {
+        constexpr int GG = decltype(G)::value;
+        auto full = [&](auto U) {
+            constexpr int UU = decltype(U)::value;
+            if (fx == 2)
+                hipLaunchKernelGGL((crc64_full_kernel<GG, UU, true>), grid, dim3(kBlock), 0, stream, a, kc);
+            else
+                hipLaunchKernelGGL((crc64_full_kernel<GG, UU, false>), grid, dim3(kBlock), 0, stream, a, kc);
+        };
+        if (!fx)
+            hipLaunchKernelGGL(crc64_batch_kernel<GG>, grid, dim3(kBlock), 0, stream, a, kc);
+        else if (fu == 4)
+            full(Int<4>{});
+        else
+            full(Int<2>{});
+    });
+}
+
+// launch_lanes for the CRC-64 copying kernels.
+template <typename L>
+int launch_copying64(uint64_t units, int g, hipStream_t stream, const char* what, L launch) {
+#if PCRC64_ABL != 0 || PCRC64_ROLL != 1 || PCRC64_U != 2
+    // A/B builds of the row loop: the copying kernels exist for the product's loop only
+    (void)launch;
+    return units == 0 ? 0 : fail(-ENOTSUP, "the copying CRC-64 kernels are not part of this A/B build");
+#else
+    return launch_lanes<Crc64>(units, g, true, stream, what, launch);
+#endif
 }
 
 // The CRC-64 copying kernels (crc64_batch_kernel<G, true>, crc64_gather_kernel<G>;
 // DESIGN.md §4.4): always the generic kernel, one build per lane-group size
 // (photon_crc_set_lanes_per_buffer and photon_crc_set_batch_grid apply; the
 // full-row kernel has no copying form). gather: units = messages.
-int launch_copy64(const CopyBatch64Args& a, bool gather, uint64_t units, int g, hipStream_t stream) {
-    if (units == 0) return 0;
-#if PCRC64_ABL != 0 || PCRC64_ROLL != 1 || PCRC64_U != 2
-    // A/B builds of the row loop: the copying kernels exist for the product's loop only
-    return fail(-ENOTSUP, "the copying CRC-64 kernels are not part of this A/B build");
-#else
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    const uint64_t gpw = 64 / g;
-    const uint64_t waves = (units + gpw - 1) / gpw;
-    uint64_t grid = (waves + kWaves - 1) / kWaves;
-    if (grid > (uint64_t)cus) grid = cus;
-    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
-    const LaneConsts64& kc = lane_consts64(g);
-    HeavyLaunch heavy(stream);
-#define LC64(GG)                                                                                                \
-    do {                                                                                                        \
-        if (gather)                                                                                             \
-            hipLaunchKernelGGL((crc64_gather_kernel<GG>), dim3(grid), dim3(kBlock), 0, stream, a, kc);          \
-        else                                                                                                    \
-            hipLaunchKernelGGL((crc64_batch_kernel<GG, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc);     \
-    } while (0)
-    switch (g) {
-        case 64: LC64(64); break;
-        case 32: LC64(32); break;
-        case 16: LC64(16); break;
-        case 8: LC64(8); break;
-        default: LC64(4); break;
-    }
-#undef LC64
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, gather ? "crc64_gather_kernel launch" : "crc64_batch_kernel<copy> launch");
-    return 0;
-#endif
+int launch_copy(const CopyBatch64Args& a, uint64_t units, int g, hipStream_t stream, bool gather = false) {
+    return launch_copying64(units, g, stream, gather ? "crc64_gather_kernel launch" : "crc64_batch_kernel<copy> launch",
+                            [&](auto G, dim3 grid, const LaneConsts64& kc) {
+        constexpr int GG = decltype(G)::value;
+        if (gather)
+            hipLaunchKernelGGL((crc64_gather_kernel<GG>), grid, dim3(kBlock), 0, stream, a, kc);
+        else
+            hipLaunchKernelGGL((crc64_batch_kernel<GG, true>), grid, dim3(kBlock), 0, stream, a, kc);
+    });
 }
 
-// crc64_copy_iov_kernel<G>, as launch_copy64.
-int launch_copy_iov64(const CopyIov64Args& a, int g, hipStream_t stream) {
-    if (a.nmsg == 0) return 0;
-#if PCRC64_ABL != 0 || PCRC64_ROLL != 1 || PCRC64_U != 2
-    return fail(-ENOTSUP, "the copying CRC-64 kernels are not part of this A/B build");
-#else
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    const uint64_t gpw = 64 / g;
-    const uint64_t waves = (a.nmsg + gpw - 1) / gpw;
-    uint64_t grid = (waves + kWaves - 1) / kWaves;
-    if (grid > (uint64_t)cus) grid = cus;
-    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
-    const LaneConsts64& kc = lane_consts64(g);
-    HeavyLaunch heavy(stream);
-    switch (g) {
-        case 64: hipLaunchKernelGGL(crc64_copy_iov_kernel<64>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
-        case 32: hipLaunchKernelGGL(crc64_copy_iov_kernel<32>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
-        case 16: hipLaunchKernelGGL(crc64_copy_iov_kernel<16>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
-        case 8: hipLaunchKernelGGL(crc64_copy_iov_kernel<8>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
-        default: hipLaunchKernelGGL(crc64_copy_iov_kernel<4>, dim3(grid), dim3(kBlock), 0, stream, a, kc); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "crc64_copy_iov_kernel launch");
-    return 0;
-#endif
+// crc64_copy_iov_kernel<G>, as launch_copy.
+int launch_copy_iov(const CopyIov64Args& a, int g, hipStream_t stream) {
+    return launch_copying64(a.nmsg, g, stream, "crc64_copy_iov_kernel launch",
+                            [&](auto G, dim3 grid, const LaneConsts64& kc) {
+        hipLaunchKernelGGL(crc64_copy_iov_kernel<decltype(G)::value>, grid, dim3(kBlock), 0, stream, a, kc);
+    });
 }
 
 // crc64_copy_iov_seg_kernel<G, DST> and the fold of its segment CRCs
-// (DESIGN.md §4.6), both on `stream`: the grid as launch_copy_iov64.
-int launch_copy_iov_seg64(const CopyIovSeg64Args& a, bool dst_side, uint64_t seed0, const uint64_t* d_seeds,
-                          uint64_t* d_out, int g, hipStream_t stream) {
-    if (a.nmsg == 0) return 0;
-#if PCRC64_ABL != 0 || PCRC64_ROLL != 1 || PCRC64_U != 2
-    return fail(-ENOTSUP, "the copying CRC-64 kernels are not part of this A/B build");
-#else
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    const uint64_t gpw = 64 / g;
-    const uint64_t waves = (a.nmsg + gpw - 1) / gpw;
-    uint64_t grid = (waves + kWaves - 1) / kWaves;
-    if (grid > (uint64_t)cus) grid = cus;
-    if (const int cap = g_grid_cap.load(std::memory_order_relaxed)) grid = grid > (uint64_t)cap ? (uint64_t)cap : grid;
-    const LaneConsts64& kc = lane_consts64(g);
-    HeavyLaunch heavy(stream);
-#define LCS64(GG)                                                                                                    \
-    do {                                                                                                             \
-        if (dst_side)                                                                                                \
-            hipLaunchKernelGGL((crc64_copy_iov_seg_kernel<GG, true>), dim3(grid), dim3(kBlock), 0, stream, a, kc);   \
-        else                                                                                                         \
-            hipLaunchKernelGGL((crc64_copy_iov_seg_kernel<GG, false>), dim3(grid), dim3(kBlock), 0, stream, a, kc);  \
-    } while (0)
-    switch (g) {
-        case 64: LCS64(64); break;
-        case 32: LCS64(32); break;
-        case 16: LCS64(16); break;
-        case 8: LCS64(8); break;
-        default: LCS64(4); break;
-    }
-#undef LCS64
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "crc64_copy_iov_seg_kernel launch");
-    hipLaunchKernelGGL(crc64_seg_fold_kernel, dim3((a.nmsg + kSegFoldBlock / 64 - 1) / (kSegFoldBlock / 64)),
-                       dim3(kSegFoldBlock), 0, stream, a, dst_side ? 1 : 0,
-                       seed0, d_seeds, d_out, pow_table64());
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "crc64_seg_fold_kernel launch");
-    return 0;
-#endif
+// (DESIGN.md §4.6), both on `stream`: the grid as launch_copy_iov. Unlike
+// the CRC-32C form, a second kernel folds: seed0, d_seeds and d_out go to it,
+// not into the copy kernel's arguments.
+int launch_copy_iov_seg(const CopyIovSeg64Args& a, bool dst_side, uint64_t seed0, const uint64_t* d_seeds,
+                        uint64_t* d_out, int g, hipStream_t stream) {
+    int copy_rc = 0;
+    const int rc = launch_copying64(a.nmsg, g, stream, "crc64_seg_fold_kernel launch",
+                                    [&](auto G, dim3 grid, const LaneConsts64& kc) {
+        constexpr int GG = decltype(G)::value;
+        if (dst_side)
+            hipLaunchKernelGGL((crc64_copy_iov_seg_kernel<GG, true>), grid, dim3(kBlock), 0, stream, a, kc);
+        else
+            hipLaunchKernelGGL((crc64_copy_iov_seg_kernel<GG, false>), grid, dim3(kBlock), 0, stream, a, kc);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {  // no fold after a copy kernel that was not enqueued
+            copy_rc = hip_fail(e, "crc64_copy_iov_seg_kernel launch");
+            return;
+        }
+        // inside the copy kernel's HeavyLaunch mark
+        hipLaunchKernelGGL(crc64_seg_fold_kernel, dim3((a.nmsg + kSegFoldBlock / 64 - 1) / (kSegFoldBlock / 64)),
+                           dim3(kSegFoldBlock), 0, stream, a, dst_side ? 1 : 0,
+                           seed0, d_seeds, d_out, pow_table<Crc64>());
+    });
+    return copy_rc ? copy_rc : rc;
 }
 
 // Host-memory pipeline (photon_crc32c_host_batch_strided): per device, a copy
@@ -1100,14 +1106,22 @@ std::string long_state_diag(hipStream_t st) {
     return "; reduce ticket " + std::to_string(ticket) + ", expected " + std::to_string(ls->base);
 }
 
-// Enqueue a long launch on its state: `launch(state, base, reset)` returns
-// the hipError_t of the enqueue; a persistent state's base advances by the
-// grid only when the launch was enqueued, under its lock (launch order).
-template <typename L>
-int long_launch(hipStream_t st, uint64_t grid, const char* what, L launch) {
+// Enqueue a long launch on its state: the state goes into the kernel's
+// arguments `a` (acc, tbase, treset), then enqueue() launches the kernel with
+// them; a persistent state's base advances by the grid only when the launch
+// was enqueued, under its lock (launch order). kernel + what: the error text.
+template <typename A, typename L>
+int long_launch(hipStream_t st, uint64_t grid, const char* kernel, const char* what, A& a, L enqueue) {
+    auto launch = [&](void* state, uint64_t base, uint32_t reset) {
+        a.acc = static_cast<decltype(a.acc)>(state);
+        a.tbase = base;
+        a.treset = reset;
+        enqueue();
+        return hipGetLastError();
+    };
     if (grid <= 1) {
         const hipError_t e = launch(nullptr, 0ull, 0u);
-        return e == hipSuccess ? 0 : hip_fail(e, what);
+        return e == hipSuccess ? 0 : hip_fail(e, kernel, what);
     }
     bool capturing = false;
     if (int rc = capture_status(st, &capturing)) return rc;
@@ -1115,7 +1129,7 @@ int long_launch(hipStream_t st, uint64_t grid, const char* what, L launch) {
         void* cs = nullptr;
         if (int rc = capture_state(st, &cs)) return rc;
         const hipError_t e = launch(cs, 0ull, 1u);
-        return e == hipSuccess ? 0 : hip_fail(e, what);
+        return e == hipSuccess ? 0 : hip_fail(e, kernel, what);
     }
     LongState* ls = nullptr;
     void* lease = nullptr;
@@ -1123,11 +1137,11 @@ int long_launch(hipStream_t st, uint64_t grid, const char* what, L launch) {
     if (lease) {
         const hipError_t e = launch(lease, 0ull, 1u);
         const int frc = scratch_free(lease, st);
-        return e != hipSuccess ? hip_fail(e, what) : frc;
+        return e != hipSuccess ? hip_fail(e, kernel, what) : frc;
     }
     std::lock_guard<std::mutex> lk(ls->mu);
     const hipError_t e = launch(ls->p, ls->base, 0u);
-    if (e != hipSuccess) return hip_fail(e, what);
+    if (e != hipSuccess) return hip_fail(e, kernel, what);
     ls->base += grid;
     return 0;
 }
@@ -1137,7 +1151,8 @@ int long_launch(hipStream_t st, uint64_t grid, const char* what, L launch) {
 // buffer"): its LDS tables and basis words, computed on the host with gf2.h
 // and copied to each device once, on that device's first small call (a
 // private non-blocking stream, so no other stream is synchronised).
-PerDevice<uint32_t*> g_img;
+template <typename W>
+PerDevice<typename W::T*> g_img;
 
 std::vector<uint32_t> small_image_host() {
     std::vector<uint32_t> img(kSmImage / 4, 0u);
@@ -1181,20 +1196,8 @@ int upload_image(const std::vector<T>& host, uint64_t bytes, T** out, const char
     return 0;
 }
 
-// The image of device `dev` (the caller's current device: multi-device paths
-// set it first, multi_device.h).
-int small_image(int dev, const uint32_t** out) {
-    uint32_t* p = nullptr;
-    const int rc = g_img.get(dev, &p, [](int, uint32_t*& slot) {
-        static const std::vector<uint32_t> host = small_image_host();
-        return upload_image(host, kSmImage, &slot, "small-buffer table image");
-    });
-    *out = p;
-    return rc;
-}
-
 // The CRC-64 small kernel's image (crc64_kernels.h crc64_small_kernel), as
-// small_image: nibble tables [position][value] of x^64, x^(128 V), x^(64 +
+// small_image_host: nibble tables [position][value] of x^64, x^(128 V), x^(64 +
 // 128 dl), x^(1024 dh), then the wave and tail basis words.
 std::vector<uint64_t> small64_image_host() {
     std::vector<uint64_t> img(kSm64Image / 8, 0ull);
@@ -1218,47 +1221,29 @@ std::vector<uint64_t> small64_image_host() {
     return img;
 }
 
-PerDevice<uint64_t*> g_img64;
-
-int small64_image(int dev, const uint64_t** out) {
-    uint64_t* p = nullptr;
-    const int rc = g_img64.get(dev, &p, [](int, uint64_t*& slot) {
-        static const std::vector<uint64_t> host = small64_image_host();
-        return upload_image(host, kSm64Image, &slot, "CRC-64 small-buffer table image");
+// The image of device `dev` (the caller's current device: multi-device paths
+// set it first, multi_device.h).
+template <typename W>
+int small_image(int dev, const typename W::T** out) {
+    typename W::T* p = nullptr;
+    const int rc = g_img<W>.get(dev, &p, [](int, typename W::T*& slot) {
+        static const std::vector<typename W::T> host = W::image_host();
+        return upload_image(host, W::kImageBytes, &slot, W::kImageName);
     });
     *out = p;
     return rc;
-}
-
-// The CRC-64 small kernel's geometry (as small_args; the grid covers the
-// init's 8 bytes).
-bool small64_args(const void* p, uint64_t n, uint64_t seed, Small64Args* a, uint32_t* grid,
-                  uint64_t max_blocks = kSmallBlocks) {
-    const uintptr_t d = reinterpret_cast<uintptr_t>(p);
-    const uint64_t s0 = d & 15u, eoff = s0 + n;
-    const uint64_t cover = eoff > s0 + 8 ? eoff : s0 + 8;
-    const uint64_t nb = (cover + 15) >> 4;
-    if (nb > max_blocks) return false;
-    a->a0 = reinterpret_cast<const uint8_t*>(d - s0);
-    a->nb = (uint32_t)nb;
-    a->s0 = (uint32_t)s0;
-    a->eoff = (uint32_t)eoff;
-    a->k = (uint32_t)(16 * nb - eoff);
-    a->init = ~seed;
-    *grid = nb > kSmallLanes ? kSmallWg : (uint32_t)((nb + 255) / 256);
-    a->wg0 = kSmallWg - *grid;
-    return true;
 }
 
 // The small kernel's geometry for [p, p + n), or false when the block span
 // exceeds max_blocks (kSmallBlocks: the long kernel's case; the service takes
 // up to kSvcMaxBlocks). *grid = the workgroups that
 // hold data (the last ones of the layout).
-bool small_args(const void* p, uint64_t n, uint32_t seed, SmallArgs* a, uint32_t* grid,
-                  uint64_t max_blocks = kSmallBlocks) {
+template <typename W>
+bool small_args(const void* p, uint64_t n, typename W::T seed, typename W::Small* a, uint32_t* grid,
+                uint64_t max_blocks = kSmallBlocks) {
     const uintptr_t d = reinterpret_cast<uintptr_t>(p);
     const uint64_t s0 = d & 15u, eoff = s0 + n;
-    const uint64_t cover = eoff > s0 + 4 ? eoff : s0 + 4;  // the seed's 4 bytes lie inside the grid
+    const uint64_t cover = eoff > s0 + W::kSeedBytes ? eoff : s0 + W::kSeedBytes;  // the seed's bytes lie inside the grid
     const uint64_t nb = (cover + 15) >> 4;
     if (nb > max_blocks) return false;
     a->a0 = reinterpret_cast<const uint8_t*>(d - s0);
@@ -1266,7 +1251,7 @@ bool small_args(const void* p, uint64_t n, uint32_t seed, SmallArgs* a, uint32_t
     a->s0 = (uint32_t)s0;
     a->eoff = (uint32_t)eoff;
     a->k = (uint32_t)(16 * nb - eoff);
-    a->seed = seed;
+    W::put_seed(a, seed);
     *grid = nb > kSmallLanes ? kSmallWg : (uint32_t)((nb + 255) / 256);
     a->wg0 = kSmallWg - *grid;
     return true;
@@ -1277,34 +1262,300 @@ bool small_args(const void* p, uint64_t n, uint32_t seed, SmallArgs* a, uint32_t
 // photon_crc_set_mid_kernel is on, else false (the long kernel's case).
 std::atomic<int> g_mid_kernel{1};
 
-template <typename A, typename Fit>
-bool mid_layout(A* a, uint32_t* grid, Fit fit) {
-    if (!g_mid_kernel.load(std::memory_order_relaxed) || !fit()) return false;
+template <typename W>
+bool mid_args(const void* p, uint64_t n, typename W::T seed, typename W::Small* a, uint32_t* grid) {
+    if (!g_mid_kernel.load(std::memory_order_relaxed) || !small_args<W>(p, n, seed, a, grid, W::kMidBlocks))
+        return false;
     *grid = a->nb > kMidLanes ? kMidWg : (a->nb + 255) / 256;
     a->wg0 = kMidWg - *grid;
     return true;
 }
-bool mid_args(const void* p, uint64_t n, uint32_t seed, SmallArgs* a, uint32_t* grid) {
-    return mid_layout(a, grid, [&] { return small_args(p, n, seed, a, grid, kMidBlocks); });
+
+// The long kernel for photon_crc32c_extend_device / photon_crc64ecma_extend_device
+// (and, with a tag, for a routed call whose result lands tagged in pinned memory).
+template <typename W>
+int extend_device_long(const void* d_data, uint64_t nbytes, typename W::T seed, typename W::T* d_out, hipStream_t st,
+                       int cus, uint32_t tag) {
+    const LongPlan lp = long_plan(d_data, nbytes, cus, W::kCrc64);
+    const LongPowers& pw = long_powers(lp, W::kCrc64);
+    typename W::Long a{};
+    W::long_args(&a, lp, pw, d_data, seed, d_out);
+    a.out_tag = tag;
+    HeavyLaunch heavy(st);
+    return long_launch(st, lp.grid, W::kKernel, "_long_kernel launch", a, [&] {
+        if (lp.lanes == 32)
+            hipLaunchKernelGGL(W::template long_kernel<32>(), dim3(lp.grid), dim3(kBlock), 0, st, a, W::lanes(32));
+        else
+            hipLaunchKernelGGL(W::template long_kernel<64>(), dim3(lp.grid), dim3(kBlock), 0, st, a, W::lanes(64));
+    });
 }
-bool mid64_args(const void* p, uint64_t n, uint64_t seed, Small64Args* a, uint32_t* grid) {
-    return mid_layout(a, grid, [&] { return small64_args(p, n, seed, a, grid, kMid64Blocks); });
+
+// A span over the small kernel's: the mid layout up to 16 MiB, else the long
+// kernel (tag: as extend_device_long).
+template <typename W>
+int extend_device_big(int dev, const void* d_data, uint64_t nbytes, typename W::T seed, typename W::T* d_out,
+                      hipStream_t st, int cus, uint32_t tag) {
+    typename W::Small sa{};
+    uint32_t grid = 0;
+    if (!mid_args<W>(d_data, nbytes, seed, &sa, &grid))
+        return extend_device_long<W>(d_data, nbytes, seed, d_out, st, cus, tag);
+    if (int rc = small_image<W>(dev, &sa.image)) return rc;
+    sa.out = d_out;
+    sa.tag = tag;  // slots unset: the tag goes to long_reduce's result word(s)
+    return long_launch(st, grid, W::kKernel, "_small_kernel (mid) launch", sa, [&] {
+        hipLaunchKernelGGL((W::template small_kernel<kMidLanes, W::kMidRows>()), dim3(grid), dim3(256), 0, st, sa);
+    });
+}
+
+// photon_crc32c_extend_device / photon_crc64ecma_extend_device.
+template <typename W>
+int extend_device(const void* d_data, uint64_t nbytes, typename W::T seed, typename W::T* d_out, void* stream) {
+    if (!d_out || (!d_data && nbytes)) return fail(-EINVAL, "null buffer or output");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    typename W::Small sa{};
+    uint32_t sgrid = 0;
+    if (small_args<W>(d_data, nbytes, seed, &sa, &sgrid)) {  // <= 256 KiB: the latency path
+        if (int rc = small_image<W>(dev, &sa.image)) return rc;
+        sa.out = d_out;
+        return long_launch(st, sgrid, W::kKernel, "_small_kernel launch", sa, [&] {
+            hipLaunchKernelGGL((W::template small_kernel<kSmallLanes, kSmallRows>()), dim3(sgrid), dim3(256), 0, st,
+                               sa);
+        });
+    }
+    return extend_device_big<W>(dev, d_data, nbytes, seed, d_out, st, cus, 0);
+}
+
+// photon_crc32c_copy_extend_device / photon_crc64ecma_copy_extend_device:
+// extend_device_long's plan, powers and state with the copying kernel. Every
+// size comes here (the plan's `small` branch serves spans up to 256 KiB).
+template <typename W>
+int copy_extend_device(const void* src, void* d_dst, uint64_t nbytes, typename W::T seed, typename W::T* d_out,
+                       void* stream) {
+    if (!d_out || ((!src || !d_dst) && nbytes)) return fail(-EINVAL, "null source, destination or output");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const LongPlan lp = long_plan(src, nbytes, cus, W::kCrc64);
+    const LongPowers& pw = long_powers(lp, W::kCrc64);
+    typename W::CopyLong a{};
+    W::long_args(&a, lp, pw, src, seed, d_out);
+    a.dst = static_cast<uint8_t*>(d_dst);
+    HeavyLaunch heavy(st);
+    return long_launch(st, lp.grid, W::kKernel, "_copy_long_kernel launch", a, [&] {
+        if (lp.lanes == 32)
+            hipLaunchKernelGGL(W::template copy_long_kernel<32>(), dim3(lp.grid), dim3(kBlock), 0, st, a,
+                               W::lanes(32));
+        else
+            hipLaunchKernelGGL(W::template copy_long_kernel<64>(), dim3(lp.grid), dim3(kBlock), 0, st, a,
+                               W::lanes(64));
+    });
+}
+
+// photon_crc32c_batch_strided / photon_crc64ecma_batch_strided.
+template <typename W>
+int batch_strided(const void* d_base, uint64_t stride, uint64_t nbytes, uint64_t count, typename W::T seed0,
+                  const typename W::T* d_seeds, typename W::T* d_out, void* stream) {
+    if (count && (!d_out || (!d_base && nbytes))) return fail(-EINVAL, "null buffer or output");
+    typename W::Batch a{};
+    a.base = static_cast<const uint8_t*>(d_base);
+    a.stride = stride;
+    a.nbytes = nbytes;
+    a.count = count;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.seed0 = seed0;
+    if (W::kShiftInit && !d_seeds && !(reinterpret_cast<uintptr_t>(d_base) & 15) && !(stride & 15) && nbytes >= 64) {
+        a.shift_init = 1;
+        a.init_shift = W::shift_init(seed0, nbytes);
+    }
+    return launch_batch(a, nbytes, static_cast<hipStream_t>(stream));
+}
+
+// photon_crc32c_batch_iov / photon_crc64ecma_batch_iov.
+template <typename W>
+int batch_iov(const photon_crc_iovec* d_iov, uint64_t count, typename W::T seed0, const typename W::T* d_seeds,
+              typename W::T* d_out, void* stream) {
+    if (count && (!d_iov || !d_out)) return fail(-EINVAL, "null descriptor array or output");
+    typename W::Batch a{};
+    a.iov = d_iov;
+    a.count = count;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.seed0 = seed0;
+    // Descriptors live on the device; lengths are unknown to the host, so the
+    // lane-group size is the generic one unless overridden.
+    return launch_batch(a, 65536, static_cast<hipStream_t>(stream));
+}
+
+// Copy + CRC in one pass (crc32c_gpu.h; DESIGN.md "Copy + CRC", §4.4):
+// photon_crc32c_copy_batch_strided / photon_crc64ecma_copy_batch_strided.
+template <typename W>
+int copy_batch_strided(const void* src_base, uint64_t src_stride, void* d_dst_base, uint64_t dst_stride,
+                       uint64_t nbytes, uint64_t count, typename W::T seed0, const typename W::T* d_seeds,
+                       typename W::T* d_out, void* stream) {
+    if (!count) return 0;
+    if (!d_out || ((!src_base || !d_dst_base) && nbytes)) return fail(-EINVAL, "null source, destination or output");
+    typename W::CopyBatch a{};
+    a.base = static_cast<const uint8_t*>(src_base);
+    a.stride = src_stride;
+    a.nbytes = nbytes;
+    a.count = count;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.seed0 = seed0;
+    a.dst_base = static_cast<uint8_t*>(d_dst_base);
+    a.dst_stride = dst_stride;
+    if (W::kShiftInit && !d_seeds && !(reinterpret_cast<uintptr_t>(src_base) & 15) && !(src_stride & 15) &&
+        nbytes >= 64) {
+        a.shift_init = 1;
+        a.init_shift = W::shift_init(seed0, nbytes);
+    }
+    return launch_copy(a, count, W::copy_lanes(nbytes), static_cast<hipStream_t>(stream));
+}
+
+// photon_crc32c_copy_batch_iov / photon_crc64ecma_copy_batch_iov.
+template <typename W>
+int copy_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t count, typename W::T seed0,
+                   const typename W::T* d_seeds, typename W::T* d_out, void* stream) {
+    if (!count) return 0;
+    if (!d_src || !d_dst || !d_out) return fail(-EINVAL, "null descriptor array, destination array or output");
+    typename W::CopyBatch a{};
+    a.iov = d_src;
+    a.count = count;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.seed0 = seed0;
+    a.dst = d_dst;
+    return launch_copy(a, count, W::copy_lanes(65536), static_cast<hipStream_t>(stream));
+}
+
+// photon_crc32c_copy_msg_iov_n / photon_crc64ecma_copy_msg_iov_n.
+template <typename W>
+int copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                   const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst, uint64_t nmsg,
+                   const uint64_t* d_size, typename W::T seed0, const typename W::T* d_seeds, typename W::T* d_out,
+                   uint64_t* d_copied, void* stream) {
+    if (!nmsg) return 0;
+    if (!d_src_start || !d_dst_start || !d_out || (!d_src && nsrc) || (!d_dst && ndst))
+        return fail(-EINVAL, "null argument");
+    // Lane groups as the gather takes (choose_lanes(8192)).
+    typename W::CopyIov a{};
+    a.src = d_src;
+    a.src_start = d_src_start;
+    a.dst = d_dst;
+    a.dst_start = d_dst_start;
+    a.nmsg = nmsg;
+    a.size = d_size;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    a.copied = d_copied;
+    a.seed0 = seed0;
+    return launch_copy_iov(a, choose_lanes(8192), static_cast<hipStream_t>(stream));
+}
+
+// photon_crc32c_combine_batch / photon_crc64ecma_combine_batch.
+template <typename W>
+int combine_batch(const typename W::T* d_crc1, const typename W::T* d_crc2, const uint32_t* d_len2, uint64_t count,
+                  typename W::T* d_out, void* stream) {
+    if (!count) return 0;
+    if (!d_crc1 || !d_crc2 || !d_len2 || !d_out) return fail(-EINVAL, "null argument");
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    hipLaunchKernelGGL(W::kCombineKernel, dim3((count + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       d_crc1, d_crc2, d_len2, count, d_out, pow_table<W>());
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, "_combine_kernel launch");
+}
+
+// photon_crc32c_trim_batch / photon_crc64ecma_trim_batch (C: photon_crc_component,
+// photon_crc64_component).
+template <typename W, typename C>
+int trim_batch(const C* d_all, const C* d_prefix, const C* d_suffix, uint64_t count, typename W::T* d_out,
+               uint32_t* d_nerr, void* stream) {
+    if (!count) return 0;
+    if (!d_all || !d_prefix || !d_suffix || !d_out) return fail(-EINVAL, "null argument");
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    hipLaunchKernelGGL(W::kTrimKernel, dim3((count + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       d_all, d_prefix, d_suffix, count, d_out, d_nerr, pow_table<W>(), rshift_table<W>());
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, "_trim_kernel launch");
+}
+
+// photon_crc32c_series_device / photon_crc64ecma_series_device: parts below
+// W::kSeriesMinPart bytes give 0 and are not read.
+template <typename W>
+int series_device(const void* d_buffer, uint32_t part_size, uint32_t n_parts, typename W::T* d_crc_parts,
+                  void* stream) {
+    if (!n_parts) return 0;
+    if (!d_crc_parts || (!d_buffer && part_size)) return fail(-EINVAL, "null buffer or output");
+    if (part_size < W::kSeriesMinPart) {
+        int cus = 0;
+        int dev = current_device(&cus);
+        if (dev < 0) return dev;
+        const hipError_t e =
+            hipMemsetAsync(d_crc_parts, 0, sizeof(typename W::T) * n_parts, static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? 0 : hip_fail(e, "hipMemsetAsync");
+    }
+    return batch_strided<W>(d_buffer, part_size, part_size, n_parts, 0, nullptr, d_crc_parts, stream);
+}
+
+// photon_crc32c_combine_series_device / photon_crc64ecma_combine_series_device.
+template <typename W>
+int combine_series_device(const typename W::T* d_crc, uint32_t part_size, uint32_t n_parts, typename W::T* d_result,
+                          void* stream) {
+    if (!d_result || (!d_crc && n_parts)) return fail(-EINVAL, "null argument");
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(d_result, 0, sizeof(typename W::T), st);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+    if (!n_parts) return 0;
+    if (!W::combine_series_of_empty(d_crc, part_size, n_parts, d_result, st)) {
+        const uint64_t threads = ((uint64_t)n_parts + kSeriesChunk - 1) / kSeriesChunk;
+        hipLaunchKernelGGL(W::kCombineSeriesKernel, dim3((threads + 255) / 256), dim3(256), 0, st, d_crc,
+                           (uint64_t)n_parts, d_result, part_pow_table<W>(part_size));
+    }
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, W::kCombineSeriesLaunch);
+}
+
+// Workgroup size of the fold_parts kernels by parts per object (the host
+// knows the average only): a wave for up to 64, 256 threads up to 1,024,
+// 1,024 threads above.
+uint32_t fold_parts_block_size(uint64_t nobj, uint64_t nparts) {
+    const uint64_t avg = nparts / nobj;
+    return avg <= 64 ? 64u : avg <= 1024 ? 256u : (uint32_t)kFoldMaxBlock;
+}
+
+// photon_crc32c_fold_parts_n / photon_crc64ecma_fold_parts_n.
+template <typename W>
+int fold_parts_n(const typename W::T* d_crc, const uint64_t* d_len, const uint64_t* d_obj_start, uint64_t nobj,
+                 uint64_t nparts, typename W::T seed0, const typename W::T* d_seeds, typename W::T* d_out,
+                 uint64_t* d_total, void* stream) {
+    if (!nobj) return 0;
+    if (!d_out) return fail(-EINVAL, "null output");
+    if ((!d_crc || !d_len) && nparts) return fail(-EINVAL, "null part CRCs or lengths");
+    if (!d_obj_start && nobj != 1) return fail(-EINVAL, "a null d_obj_start means one object: nobj must be 1");
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint32_t grid = nobj < kFoldMaxGrid ? (uint32_t)nobj : kFoldMaxGrid;
+    hipLaunchKernelGGL(W::kFoldPartsKernel, dim3(grid), dim3(fold_parts_block_size(nobj, nparts)), 0,
+                       static_cast<hipStream_t>(stream), d_crc, d_len, d_obj_start, nobj, nparts, seed0, d_seeds,
+                       d_out, d_total, pow_table<W>());
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, "_fold_parts_kernel launch");
 }
 
 }  // namespace
-
-int extend_device_long(const void* d_data, uint64_t nbytes, uint32_t seed, uint32_t* d_out, hipStream_t st, int cus,
-                       uint32_t tag);
-int extend_device_big(int dev, const void* d_data, uint64_t nbytes, uint32_t seed, uint32_t* d_out, hipStream_t st,
-                      int cus, uint32_t tag);
-int extend64_device_big(int dev, const void* d_data, uint64_t nbytes, uint64_t seed, uint64_t* d_out, hipStream_t st,
-                        int cus, uint32_t tag);
-int extend64_device_long(const void* d_data, uint64_t nbytes, uint64_t seed, uint64_t* d_out, hipStream_t st,
-                         int cus, uint32_t tag);
-int copy_extend_device_long(const void* src, void* d_dst, uint64_t nbytes, uint32_t seed, uint32_t* d_out,
-                            hipStream_t st, int cus);
-int copy_extend64_device_long(const void* src, void* d_dst, uint64_t nbytes, uint64_t seed, uint64_t* d_out,
-                              hipStream_t st, int cus);
 
 // For the other translation units of the library (internal.h).
 int report_error(int code, const char* what) { return fail(code, what); }
@@ -1361,7 +1612,7 @@ int photon_crc_test_tables(int which, uint32_t* out, int n) {
     }
     if (n < 32) return fail(-EINVAL, "short output");
     if (which == 4 || which == 5) {  // device combine / trim powers x^(+-8*2^i)
-        const PowTable& t = which == 4 ? pow_table() : rshift_table();
+        const PowTable& t = which == 4 ? pow_table<Crc32c>() : rshift_table<Crc32c>();
         for (int i = 0; i < 32; ++i) out[i] = t.x8pow2[i];
         return 32;
     }
@@ -1484,21 +1735,7 @@ int photon_crc_set_msg_rows(int rows_per_step) {
 
 int photon_crc32c_batch_strided(const void* d_base, uint64_t stride, uint64_t nbytes, uint64_t count,
                                 uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_out, void* stream) {
-    if (count && (!d_out || (!d_base && nbytes))) return fail(-EINVAL, "null buffer or output");
-    BatchArgs a{};
-    a.base = static_cast<const uint8_t*>(d_base);
-    a.stride = stride;
-    a.nbytes = nbytes;
-    a.iov = nullptr;
-    a.count = count;
-    a.seeds = d_seeds;
-    a.out = d_out;
-    a.seed0 = seed0;
-    if (PCRC_SHIFT_INIT && !d_seeds && !(reinterpret_cast<uintptr_t>(d_base) & 15) && !(stride & 15) && nbytes >= 64) {
-        a.shift_init = 1;
-        a.init_shift = mulmod(seed0, xpow(8ull * nbytes));
-    }
-    return launch_batch(a, nbytes, static_cast<hipStream_t>(stream));
+    return batch_strided<Crc32c>(d_base, stride, nbytes, count, seed0, d_seeds, d_out, stream);
 }
 
 int photon_crc32c_batch_strided_sync(const void* d_base, uint64_t stride, uint64_t nbytes, uint64_t count,
@@ -1657,16 +1894,7 @@ int photon_crc32c_batch_strided_shards(const photon_crc_shard* shards, int nshar
 
 int photon_crc32c_batch_iov(const photon_crc_iovec* d_iov, uint64_t count, uint32_t seed0,
                             const uint32_t* d_seeds, uint32_t* d_out, void* stream) {
-    if (count && (!d_iov || !d_out)) return fail(-EINVAL, "null descriptor array or output");
-    BatchArgs a{};
-    a.iov = d_iov;
-    a.count = count;
-    a.seeds = d_seeds;
-    a.out = d_out;
-    a.seed0 = seed0;
-    // Descriptors live on the device; lengths are unknown to the host, so the
-    // lane-group size is the generic one unless overridden.
-    return launch_batch(a, 65536, static_cast<hipStream_t>(stream));
+    return batch_iov<Crc32c>(d_iov, count, seed0, d_seeds, d_out, stream);
 }
 
 int photon_crc32c_batch_msg(const photon_crc_iovec* d_iov, const uint64_t* d_msg_start, uint64_t nmsg,
@@ -1710,42 +1938,29 @@ int pcrc::batch_msg_lanes(const photon_crc_iovec* d_iov, const uint64_t* d_msg_s
     const int mode = g_msg_mode.load(std::memory_order_relaxed);
     const bool fused = mode == 1 || (mode == 0 && nmsg >= 4096 * gpw && nseg <= 64 * nmsg);
     if (fused) {
-        int cus = 0;
-        int dev = current_device(&cus);
-        if (dev < 0) return dev;
         a.msg_start = d_msg_start;
         a.nmsg = nmsg;
         a.msg_out = d_out;
         a.seeds = d_seeds;
         a.seed0 = seed0;
-        uint64_t grid = ((nmsg + gpw - 1) / gpw + kWaves - 1) / kWaves;
-        if (grid > (uint64_t)cus) grid = cus;
-        const LaneConsts& kc = lane_consts(g);
-        HeavyLaunch heavy(st);
-#define LM(GG, UU)                                                                                            \
-    do {                                                                                                      \
-        if (a.out)                                                                                            \
-            hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU, 2>), dim3(grid), dim3(kBlock), 0, st, a, kc, pow_table()); \
-        else                                                                                                  \
-            hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU, 1>), dim3(grid), dim3(kBlock), 0, st, a, kc, pow_table()); \
-    } while (0)
-#define LMG(UU)                     \
-    switch (g) {                    \
-        case 64: LM(64, UU); break; \
-        case 32: LM(32, UU); break; \
-        case 16: LM(16, UU); break; \
-        case 8: LM(8, UU); break;   \
-        default: LM(4, UU); break;  \
-    }
-        if (g_msg_u.load(std::memory_order_relaxed) == 2) {
-            LMG(2)
-        } else {
-            LMG(4)
-        }
-#undef LMG
-#undef LM
-        e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "crc32c_batch_kernel<msg> launch");
+        const int rows_per_step = g_msg_u.load(std::memory_order_relaxed);
+        // capped = false: photon_crc_set_batch_grid does not apply to the fused message form
+        return launch_lanes<Crc32c>(nmsg, g, false, st, "crc32c_batch_kernel<msg> launch",
+                                    [&](auto G, dim3 grid, const LaneConsts& kc) {
+            auto rows = [&](auto U) {
+                constexpr int GG = decltype(G)::value, UU = decltype(U)::value;
+                if (a.out)
+                    hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU, 2>), grid, dim3(kBlock), 0, st, a, kc,
+                                       pow_table<Crc32c>());
+                else
+                    hipLaunchKernelGGL((crc32c_batch_kernel<GG, UU, 1>), grid, dim3(kBlock), 0, st, a, kc,
+                                       pow_table<Crc32c>());
+            };
+            if (rows_per_step == 2)
+                rows(Int<2>{});
+            else
+                rows(Int<4>{});
+        });
     }
     void* scratch = nullptr;  // segment CRCs the caller did not ask for
     if (!d_seg_out && nseg && seg_scratch) {
@@ -1758,7 +1973,7 @@ int pcrc::batch_msg_lanes(const photon_crc_iovec* d_iov, const uint64_t* d_msg_s
     if (!rc) {
         const int bs = 256;
         hipLaunchKernelGGL(crc32c_msg_fold_kernel, dim3((nmsg + bs - 1) / bs), dim3(bs), 0, st, d_iov, d_msg_start,
-                           nmsg, a.out, seed0, d_seeds, d_out, pow_table());
+                           nmsg, a.out, seed0, d_seeds, d_out, pow_table<Crc32c>());
         e = hipGetLastError();
         if (e != hipSuccess) rc = hip_fail(e, "crc32c_msg_fold_kernel launch");
     }
@@ -1781,38 +1996,13 @@ int photon_crc32c_batch_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_m
 int photon_crc32c_copy_batch_strided(const void* src_base, uint64_t src_stride, void* d_dst_base,
                                      uint64_t dst_stride, uint64_t nbytes, uint64_t count, uint32_t seed0,
                                      const uint32_t* d_seeds, uint32_t* d_out, void* stream) {
-    if (!count) return 0;
-    if (!d_out || ((!src_base || !d_dst_base) && nbytes)) return fail(-EINVAL, "null source, destination or output");
-    CopyBatchArgs a{};
-    a.base = static_cast<const uint8_t*>(src_base);
-    a.stride = src_stride;
-    a.nbytes = nbytes;
-    a.count = count;
-    a.seeds = d_seeds;
-    a.out = d_out;
-    a.seed0 = seed0;
-    a.dst_base = static_cast<uint8_t*>(d_dst_base);
-    a.dst_stride = dst_stride;
-    if (PCRC_SHIFT_INIT && !d_seeds && !(reinterpret_cast<uintptr_t>(src_base) & 15) && !(src_stride & 15) &&
-        nbytes >= 64) {
-        a.shift_init = 1;
-        a.init_shift = mulmod(seed0, xpow(8ull * nbytes));
-    }
-    return launch_copy(a, 0, count, batch_lanes(nbytes), static_cast<hipStream_t>(stream));
+    return copy_batch_strided<Crc32c>(src_base, src_stride, d_dst_base, dst_stride, nbytes, count, seed0, d_seeds,
+                                      d_out, stream);
 }
 
 int photon_crc32c_copy_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t count, uint32_t seed0,
                                  const uint32_t* d_seeds, uint32_t* d_out, void* stream) {
-    if (!count) return 0;
-    if (!d_src || !d_dst || !d_out) return fail(-EINVAL, "null descriptor array, destination array or output");
-    CopyBatchArgs a{};
-    a.iov = d_src;
-    a.count = count;
-    a.seeds = d_seeds;
-    a.out = d_out;
-    a.seed0 = seed0;
-    a.dst = d_dst;
-    return launch_copy(a, 0, count, batch_lanes(65536), static_cast<hipStream_t>(stream));
+    return copy_batch_iov<Crc32c>(d_src, d_dst, count, seed0, d_seeds, d_out, stream);
 }
 
 int photon_crc32c_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_msg_start, uint64_t nmsg,
@@ -1832,29 +2022,15 @@ int photon_crc32c_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_
     a.seeds = d_seeds;
     a.seed0 = seed0;
     a.dst = d_dst;
-    return launch_copy(a, d_seg_out ? 2 : 1, nmsg, choose_lanes(8192), static_cast<hipStream_t>(stream));
+    return launch_copy(a, nmsg, choose_lanes(8192), static_cast<hipStream_t>(stream), d_seg_out ? 2 : 1);
 }
 
 int photon_crc32c_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
                                  const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
                                  uint64_t nmsg, const uint64_t* d_size, uint32_t seed0, const uint32_t* d_seeds,
                                  uint32_t* d_out, uint64_t* d_copied, void* stream) {
-    if (!nmsg) return 0;
-    if (!d_src_start || !d_dst_start || !d_out || (!d_src && nsrc) || (!d_dst && ndst))
-        return fail(-EINVAL, "null argument");
-    // Lane groups as the gather takes (choose_lanes(8192)).
-    CopyIovArgs a{};
-    a.src = d_src;
-    a.src_start = d_src_start;
-    a.dst = d_dst;
-    a.dst_start = d_dst_start;
-    a.nmsg = nmsg;
-    a.size = d_size;
-    a.seeds = d_seeds;
-    a.out = d_out;
-    a.copied = d_copied;
-    a.seed0 = seed0;
-    return launch_copy_iov(a, choose_lanes(8192), static_cast<hipStream_t>(stream));
+    return copy_msg_iov_n<Crc32c>(d_src, d_src_start, nsrc, d_dst, d_dst_start, ndst, nmsg, d_size, seed0, d_seeds,
+                                  d_out, d_copied, stream);
 }
 
 int photon_crc32c_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
@@ -1885,60 +2061,23 @@ int photon_crc32c_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uint64
 
 int photon_crc64ecma_batch_strided(const void* d_base, uint64_t stride, uint64_t nbytes, uint64_t count,
                                    uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out, void* stream) {
-    if (count && (!d_out || (!d_base && nbytes))) return fail(-EINVAL, "null buffer or output");
-    Batch64Args a{};
-    a.base = static_cast<const uint8_t*>(d_base);
-    a.stride = stride;
-    a.nbytes = nbytes;
-    a.count = count;
-    a.seeds = d_seeds;
-    a.out = d_out;
-    a.seed0 = seed0;
-    if (PCRC64_SHIFT_INIT && !d_seeds && !(reinterpret_cast<uintptr_t>(d_base) & 15) && !(stride & 15) &&
-        nbytes >= 64) {
-        a.shift_init = 1;
-        a.init_shift = mulmod64(~seed0, xpow64(8ull * nbytes));
-    }
-    return launch_batch64(a, nbytes, static_cast<hipStream_t>(stream));
+    return batch_strided<Crc64>(d_base, stride, nbytes, count, seed0, d_seeds, d_out, stream);
 }
 
 int photon_crc64ecma_batch_iov(const photon_crc_iovec* d_iov, uint64_t count, uint64_t seed0,
                                const uint64_t* d_seeds, uint64_t* d_out, void* stream) {
-    if (count && (!d_iov || !d_out)) return fail(-EINVAL, "null descriptor array or output");
-    Batch64Args a{};
-    a.iov = d_iov;
-    a.count = count;
-    a.seeds = d_seeds;
-    a.out = d_out;
-    a.seed0 = seed0;
-    return launch_batch64(a, 65536, static_cast<hipStream_t>(stream));
+    return batch_iov<Crc64>(d_iov, count, seed0, d_seeds, d_out, stream);
 }
 
 int photon_crc64ecma_combine_batch(const uint64_t* d_crc1, const uint64_t* d_crc2, const uint32_t* d_len2,
                                    uint64_t count, uint64_t* d_out, void* stream) {
-    if (!count) return 0;
-    if (!d_crc1 || !d_crc2 || !d_len2 || !d_out) return fail(-EINVAL, "null argument");
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    hipLaunchKernelGGL(crc64_combine_kernel, dim3((count + 255) / 256), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), d_crc1, d_crc2, d_len2, count, d_out, pow_table64());
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "crc64_combine_kernel launch");
+    return combine_batch<Crc64>(d_crc1, d_crc2, d_len2, count, d_out, stream);
 }
 
 int photon_crc64ecma_trim_batch(const photon_crc64_component* d_all, const photon_crc64_component* d_prefix,
                                 const photon_crc64_component* d_suffix, uint64_t count, uint64_t* d_out,
                                 uint32_t* d_nerr, void* stream) {
-    if (!count) return 0;
-    if (!d_all || !d_prefix || !d_suffix || !d_out) return fail(-EINVAL, "null argument");
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    hipLaunchKernelGGL(crc64_trim_kernel, dim3((count + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       d_all, d_prefix, d_suffix, count, d_out, d_nerr, pow_table64(), rshift_table64());
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "crc64_trim_kernel launch");
+    return trim_batch<Crc64>(d_all, d_prefix, d_suffix, count, d_out, d_nerr, stream);
 }
 
 int photon_crc64ecma_batch_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_msg_start, uint64_t nmsg,
@@ -1958,10 +2097,10 @@ int photon_crc64ecma_batch_msg_n(const photon_crc_iovec* d_iov, const uint64_t* 
     a.count = nseg;
     a.out = d_seg_out;
     a.seed0 = 0;
-    int rc = launch_batch64(a, 8192, st);
+    int rc = launch_batch(a, 8192, st);
     if (!rc) {
         hipLaunchKernelGGL(crc64_msg_fold_kernel, dim3((nmsg + 255) / 256), dim3(256), 0, st, d_iov, d_msg_start,
-                           nmsg, d_seg_out, seed0, d_seeds, d_out, pow_table64());
+                           nmsg, d_seg_out, seed0, d_seeds, d_out, pow_table<Crc64>());
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = hip_fail(e, "crc64_msg_fold_kernel launch");
     }
@@ -1976,38 +2115,13 @@ int photon_crc64ecma_batch_msg_n(const photon_crc_iovec* d_iov, const uint64_t* 
 int photon_crc64ecma_copy_batch_strided(const void* src_base, uint64_t src_stride, void* d_dst_base,
                                         uint64_t dst_stride, uint64_t nbytes, uint64_t count, uint64_t seed0,
                                         const uint64_t* d_seeds, uint64_t* d_out, void* stream) {
-    if (!count) return 0;
-    if (!d_out || ((!src_base || !d_dst_base) && nbytes)) return fail(-EINVAL, "null source, destination or output");
-    CopyBatch64Args a{};
-    a.base = static_cast<const uint8_t*>(src_base);
-    a.stride = src_stride;
-    a.nbytes = nbytes;
-    a.count = count;
-    a.seeds = d_seeds;
-    a.out = d_out;
-    a.seed0 = seed0;
-    a.dst_base = static_cast<uint8_t*>(d_dst_base);
-    a.dst_stride = dst_stride;
-    if (PCRC64_SHIFT_INIT && !d_seeds && !(reinterpret_cast<uintptr_t>(src_base) & 15) && !(src_stride & 15) &&
-        nbytes >= 64) {
-        a.shift_init = 1;
-        a.init_shift = mulmod64(~seed0, xpow64(8ull * nbytes));
-    }
-    return launch_copy64(a, false, count, choose_lanes(nbytes), static_cast<hipStream_t>(stream));
+    return copy_batch_strided<Crc64>(src_base, src_stride, d_dst_base, dst_stride, nbytes, count, seed0, d_seeds,
+                                     d_out, stream);
 }
 
 int photon_crc64ecma_copy_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t count,
                                     uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out, void* stream) {
-    if (!count) return 0;
-    if (!d_src || !d_dst || !d_out) return fail(-EINVAL, "null descriptor array, destination array or output");
-    CopyBatch64Args a{};
-    a.iov = d_src;
-    a.count = count;
-    a.seeds = d_seeds;
-    a.out = d_out;
-    a.seed0 = seed0;
-    a.dst = d_dst;
-    return launch_copy64(a, false, count, choose_lanes(65536), static_cast<hipStream_t>(stream));
+    return copy_batch_iov<Crc64>(d_src, d_dst, count, seed0, d_seeds, d_out, stream);
 }
 
 int photon_crc64ecma_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_msg_start, uint64_t nmsg,
@@ -2030,10 +2144,10 @@ int photon_crc64ecma_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t*
     a.seeds = d_seeds;
     a.seed0 = seed0;
     a.dst = d_dst;
-    int rc = launch_copy64(a, true, nmsg, choose_lanes(8192), st);
+    int rc = launch_copy(a, nmsg, choose_lanes(8192), st, /*gather=*/true);
     if (!rc && d_seg_out) {
         hipLaunchKernelGGL(crc64_msg_fold_kernel, dim3((nmsg + 255) / 256), dim3(256), 0, st, d_iov, d_msg_start,
-                           nmsg, d_seg_out, seed0, d_seeds, d_out, pow_table64());
+                           nmsg, d_seg_out, seed0, d_seeds, d_out, pow_table<Crc64>());
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = hip_fail(e, "crc64_msg_fold_kernel launch");
     }
@@ -2044,21 +2158,8 @@ int photon_crc64ecma_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_
                                     const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
                                     uint64_t nmsg, const uint64_t* d_size, uint64_t seed0, const uint64_t* d_seeds,
                                     uint64_t* d_out, uint64_t* d_copied, void* stream) {
-    if (!nmsg) return 0;
-    if (!d_src_start || !d_dst_start || !d_out || (!d_src && nsrc) || (!d_dst && ndst))
-        return fail(-EINVAL, "null argument");
-    CopyIov64Args a{};
-    a.src = d_src;
-    a.src_start = d_src_start;
-    a.dst = d_dst;
-    a.dst_start = d_dst_start;
-    a.nmsg = nmsg;
-    a.size = d_size;
-    a.seeds = d_seeds;
-    a.out = d_out;
-    a.copied = d_copied;
-    a.seed0 = seed0;
-    return launch_copy_iov64(a, choose_lanes(8192), static_cast<hipStream_t>(stream));
+    return copy_msg_iov_n<Crc64>(d_src, d_src_start, nsrc, d_dst, d_dst_start, ndst, nmsg, d_size, seed0, d_seeds,
+                                 d_out, d_copied, stream);
 }
 
 int photon_crc64ecma_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
@@ -2080,240 +2181,55 @@ int photon_crc64ecma_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uin
     a.size = d_size;
     a.seg_out = d_seg_out;
     a.copied = d_copied;
-    return launch_copy_iov_seg64(a, seg_side == PHOTON_CRC_SEG_OF_DST, seed0, d_seeds, d_out, choose_lanes(8192),
-                                 static_cast<hipStream_t>(stream));
+    return launch_copy_iov_seg(a, seg_side == PHOTON_CRC_SEG_OF_DST, seed0, d_seeds, d_out, choose_lanes(8192),
+                               static_cast<hipStream_t>(stream));
 }
 
 int photon_crc64ecma_extend_device(const void* d_data, uint64_t nbytes, uint64_t seed, uint64_t* d_out,
                                    void* stream) {
-    if (!d_out || (!d_data && nbytes)) return fail(-EINVAL, "null buffer or output");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    Small64Args sa{};
-    uint32_t sgrid = 0;
-    if (small64_args(d_data, nbytes, seed, &sa, &sgrid)) {  // <= 256 KiB: the latency path
-        if (int rc = small64_image(dev, &sa.image)) return rc;
-        sa.out = d_out;
-        return long_launch(st, sgrid, "crc64_small_kernel launch", [&](void* state, uint64_t base, uint32_t reset) {
-            sa.acc = static_cast<uint64_t*>(state);
-            sa.tbase = base;
-            sa.treset = reset;
-            hipLaunchKernelGGL((crc64_small_kernel<kSmallLanes, kSmallRows>), dim3(sgrid), dim3(256), 0, st, sa);
-            return hipGetLastError();
-        });
-    }
-    return pcrc::extend64_device_big(dev, d_data, nbytes, seed, d_out, st, cus, 0);
+    return extend_device<Crc64>(d_data, nbytes, seed, d_out, stream);
 }
-}  // extern "C"
-
-namespace pcrc {
-// A span over the small kernel's: the mid layout up to 16 MiB, else the long
-// kernel (tag: as extend64_device_long).
-int extend64_device_big(int dev, const void* d_data, uint64_t nbytes, uint64_t seed, uint64_t* d_out, hipStream_t st,
-                        int cus, uint32_t tag) {
-    Small64Args sa{};
-    uint32_t grid = 0;
-    if (!mid64_args(d_data, nbytes, seed, &sa, &grid))
-        return extend64_device_long(d_data, nbytes, seed, d_out, st, cus, tag);
-    if (int rc = small64_image(dev, &sa.image)) return rc;
-    sa.out = d_out;
-    sa.tag = tag;  // slots unset: the tag goes to long_reduce's result words
-    return long_launch(st, grid, "crc64_small_kernel (mid) launch", [&](void* state, uint64_t base, uint32_t reset) {
-        sa.acc = static_cast<uint64_t*>(state);
-        sa.tbase = base;
-        sa.treset = reset;
-        hipLaunchKernelGGL((crc64_small_kernel<kMidLanes, kMid64Rows>), dim3(grid), dim3(256), 0, st, sa);
-        return hipGetLastError();
-    });
-}
-
-// The long kernel for photon_crc64ecma_extend_device (tag: as extend_device_long).
-int extend64_device_long(const void* d_data, uint64_t nbytes, uint64_t seed, uint64_t* d_out, hipStream_t st,
-                         int cus, uint32_t tag) {
-    const LongPlan lp = long_plan(d_data, nbytes, cus, true);
-    const LongPowers& pw = long_powers(lp, true);
-    Long64Args a{};
-    long_args64(&a, lp, pw, d_data, seed, d_out);
-    a.out_tag = tag;
-    HeavyLaunch heavy(st);
-    return long_launch(st, lp.grid, "crc64_long_kernel launch", [&](void* state, uint64_t base, uint32_t reset) {
-        a.acc = static_cast<uint64_t*>(state);
-        a.tbase = base;
-        a.treset = reset;
-        if (lp.lanes == 32)
-            hipLaunchKernelGGL((crc64_long_kernel<32>), dim3(lp.grid), dim3(kBlock), 0, st, a, lane_consts64(32));
-        else
-            hipLaunchKernelGGL((crc64_long_kernel<64>), dim3(lp.grid), dim3(kBlock), 0, st, a, lane_consts64(64));
-        return hipGetLastError();
-    });
-}
-
-// photon_crc64ecma_copy_extend_device: extend64_device_long's plan, powers and
-// state with the copying kernel. Every size comes here (the plan's `small`
-// branch serves spans up to 256 KiB).
-int copy_extend64_device_long(const void* src, void* d_dst, uint64_t nbytes, uint64_t seed, uint64_t* d_out,
-                              hipStream_t st, int cus) {
-    const LongPlan lp = long_plan(src, nbytes, cus, true);
-    const LongPowers& pw = long_powers(lp, true);
-    CopyLong64Args a{};
-    long_args64(&a, lp, pw, src, seed, d_out);
-    a.dst = static_cast<uint8_t*>(d_dst);
-    HeavyLaunch heavy(st);
-    return long_launch(st, lp.grid, "crc64_copy_long_kernel launch", [&](void* state, uint64_t base, uint32_t reset) {
-        a.acc = static_cast<uint64_t*>(state);
-        a.tbase = base;
-        a.treset = reset;
-        if (lp.lanes == 32)
-            hipLaunchKernelGGL((crc64_copy_long_kernel<32>), dim3(lp.grid), dim3(kBlock), 0, st, a, lane_consts64(32));
-        else
-            hipLaunchKernelGGL((crc64_copy_long_kernel<64>), dim3(lp.grid), dim3(kBlock), 0, st, a, lane_consts64(64));
-        return hipGetLastError();
-    });
-}
-}  // namespace pcrc
-
-extern "C" {
 
 int photon_crc64ecma_copy_extend_device(const void* src, void* d_dst, uint64_t nbytes, uint64_t seed, uint64_t* d_out,
                                         void* stream) {
-    if (!d_out || ((!src || !d_dst) && nbytes)) return fail(-EINVAL, "null source, destination or output");
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    return pcrc::copy_extend64_device_long(src, d_dst, nbytes, seed, d_out, static_cast<hipStream_t>(stream), cus);
+    return copy_extend_device<Crc64>(src, d_dst, nbytes, seed, d_out, stream);
 }
 
 int photon_crc32c_combine_batch(const uint32_t* d_crc1, const uint32_t* d_crc2, const uint32_t* d_len2,
                                 uint64_t count, uint32_t* d_out, void* stream) {
-    if (!count) return 0;
-    if (!d_crc1 || !d_crc2 || !d_len2 || !d_out) return fail(-EINVAL, "null argument");
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    const int bs = 256;
-    hipLaunchKernelGGL(crc32c_combine_kernel, dim3((count + bs - 1) / bs), dim3(bs), 0,
-                       static_cast<hipStream_t>(stream), d_crc1, d_crc2, d_len2, count, d_out, pow_table());
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "crc32c_combine_kernel launch");
-    return 0;
+    return combine_batch<Crc32c>(d_crc1, d_crc2, d_len2, count, d_out, stream);
 }
 
 int photon_crc32c_series_device(const void* d_buffer, uint32_t part_size, uint32_t n_parts, uint32_t* d_crc_parts,
                                 void* stream) {
-    if (!n_parts) return 0;
-    if (!d_crc_parts || (!d_buffer && part_size)) return fail(-EINVAL, "null buffer or output");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (part_size < 8) {  // crc32c_series_hw (crc.cpp:481-500) leaves such parts at 0
-        int cus = 0;
-        int dev = current_device(&cus);
-        if (dev < 0) return dev;
-        hipError_t e = hipMemsetAsync(d_crc_parts, 0, 4ull * n_parts, st);
-        return e == hipSuccess ? 0 : hip_fail(e, "hipMemsetAsync");
-    }
-    return photon_crc32c_batch_strided(d_buffer, part_size, part_size, n_parts, 0, nullptr, d_crc_parts, stream);
+    return series_device<Crc32c>(d_buffer, part_size, n_parts, d_crc_parts, stream);
 }
 
 int photon_crc32c_combine_series_device(const uint32_t* d_crc, uint32_t part_size, uint32_t n_parts,
                                         uint32_t* d_result, void* stream) {
-    if (!d_result || (!d_crc && n_parts)) return fail(-EINVAL, "null argument");
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(d_result, 0, 4, st);
-    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
-    if (!n_parts) return 0;
-    if (!part_size) {
-        hipLaunchKernelGGL(crc32c_first_nonzero_kernel, dim3(1), dim3(1024), 0, st, d_crc, (uint64_t)n_parts,
-                           d_result);
-    } else {
-        const uint64_t threads = ((uint64_t)n_parts + kSeriesChunk - 1) / kSeriesChunk;
-        hipLaunchKernelGGL(crc32c_combine_series_kernel, dim3((threads + 255) / 256), dim3(256), 0, st, d_crc,
-                           (uint64_t)n_parts, d_result, part_pow_table(part_size));
-    }
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "combine_series kernel launch");
+    return combine_series_device<Crc32c>(d_crc, part_size, n_parts, d_result, stream);
 }
 
 int photon_crc64ecma_series_device(const void* d_buffer, uint32_t part_size, uint32_t n_parts, uint64_t* d_crc_parts,
                                    void* stream) {
-    if (!n_parts) return 0;
-    if (!d_crc_parts || (!d_buffer && part_size)) return fail(-EINVAL, "null buffer or output");
-    if (!part_size) {  // crc64ecma of no bytes: 0; nothing is read
-        int cus = 0;
-        int dev = current_device(&cus);
-        if (dev < 0) return dev;
-        hipError_t e = hipMemsetAsync(d_crc_parts, 0, 8ull * n_parts, static_cast<hipStream_t>(stream));
-        return e == hipSuccess ? 0 : hip_fail(e, "hipMemsetAsync");
-    }
-    return photon_crc64ecma_batch_strided(d_buffer, part_size, part_size, n_parts, 0, nullptr, d_crc_parts, stream);
+    return series_device<Crc64>(d_buffer, part_size, n_parts, d_crc_parts, stream);
 }
 
 int photon_crc64ecma_combine_series_device(const uint64_t* d_crc, uint32_t part_size, uint32_t n_parts,
                                            uint64_t* d_result, void* stream) {
-    if (!d_result || (!d_crc && n_parts)) return fail(-EINVAL, "null argument");
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(d_result, 0, 8, st);
-    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
-    if (!n_parts) return 0;
-    const uint64_t threads = ((uint64_t)n_parts + kSeriesChunk - 1) / kSeriesChunk;
-    hipLaunchKernelGGL(crc64_combine_series_kernel, dim3((threads + 255) / 256), dim3(256), 0, st, d_crc,
-                       (uint64_t)n_parts, d_result, part_pow_table64(part_size));
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "crc64_combine_series_kernel launch");
-}
-
-// Workgroup size of the fold_parts kernels by parts per object (the host
-// knows the average only): a wave for up to 64, 256 threads up to 1,024,
-// 1,024 threads above.
-static uint32_t fold_parts_block_size(uint64_t nobj, uint64_t nparts) {
-    const uint64_t avg = nparts / nobj;
-    return avg <= 64 ? 64u : avg <= 1024 ? 256u : (uint32_t)kFoldMaxBlock;
-}
-
-static int fold_parts_check(const void* d_crc, const void* d_len, const void* d_obj_start, uint64_t nobj,
-                            uint64_t nparts, const void* d_out) {
-    if (!d_out) return fail(-EINVAL, "null output");
-    if ((!d_crc || !d_len) && nparts) return fail(-EINVAL, "null part CRCs or lengths");
-    if (!d_obj_start && nobj != 1) return fail(-EINVAL, "a null d_obj_start means one object: nobj must be 1");
-    return 0;
+    return combine_series_device<Crc64>(d_crc, part_size, n_parts, d_result, stream);
 }
 
 int photon_crc32c_fold_parts_n(const uint32_t* d_crc, const uint64_t* d_len, const uint64_t* d_obj_start,
                                uint64_t nobj, uint64_t nparts, uint32_t seed0, const uint32_t* d_seeds,
                                uint32_t* d_out, uint64_t* d_total, void* stream) {
-    if (!nobj) return 0;
-    if (int rc = fold_parts_check(d_crc, d_len, d_obj_start, nobj, nparts, d_out)) return rc;
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    const uint32_t grid = nobj < kFoldMaxGrid ? (uint32_t)nobj : kFoldMaxGrid;
-    hipLaunchKernelGGL(crc32c_fold_parts_kernel, dim3(grid), dim3(fold_parts_block_size(nobj, nparts)), 0,
-                       static_cast<hipStream_t>(stream), d_crc, d_len, d_obj_start, nobj, nparts, seed0, d_seeds,
-                       d_out, d_total, pow_table());
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "crc32c_fold_parts_kernel launch");
+    return fold_parts_n<Crc32c>(d_crc, d_len, d_obj_start, nobj, nparts, seed0, d_seeds, d_out, d_total, stream);
 }
 
 int photon_crc64ecma_fold_parts_n(const uint64_t* d_crc, const uint64_t* d_len, const uint64_t* d_obj_start,
                                   uint64_t nobj, uint64_t nparts, uint64_t seed0, const uint64_t* d_seeds,
                                   uint64_t* d_out, uint64_t* d_total, void* stream) {
-    if (!nobj) return 0;
-    if (int rc = fold_parts_check(d_crc, d_len, d_obj_start, nobj, nparts, d_out)) return rc;
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    const uint32_t grid = nobj < kFoldMaxGrid ? (uint32_t)nobj : kFoldMaxGrid;
-    hipLaunchKernelGGL(crc64_fold_parts_kernel, dim3(grid), dim3(fold_parts_block_size(nobj, nparts)), 0,
-                       static_cast<hipStream_t>(stream), d_crc, d_len, d_obj_start, nobj, nparts, seed0, d_seeds,
-                       d_out, d_total, pow_table64());
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "crc64_fold_parts_kernel launch");
+    return fold_parts_n<Crc64>(d_crc, d_len, d_obj_start, nobj, nparts, seed0, d_seeds, d_out, d_total, stream);
 }
 
 // tuning.h, bench only: what a caller did before fold_parts_n existed.
@@ -2349,130 +2265,26 @@ int photon_crc_test_fold_parts(int crc64, const void* crc, const uint64_t* len, 
     if (!result || !nthreads || ((!crc || !len) && count)) return fail(-EINVAL, "null argument or no threads");
     if (crc64)
         *result = fold_replay<Gf64>(static_cast<const uint64_t*>(crc), len, count, seed, nthreads,
-                                    pow_table64().x8pow2, total);
+                                    pow_table<Crc64>().x8pow2, total);
     else
         *result = fold_replay<Gf32>(static_cast<const uint32_t*>(crc), len, count, (uint32_t)seed, nthreads,
-                                    pow_table().x8pow2, total);
+                                    pow_table<Crc32c>().x8pow2, total);
     return 0;
 }
 
 int photon_crc32c_trim_batch(const photon_crc_component* d_all, const photon_crc_component* d_prefix,
                              const photon_crc_component* d_suffix, uint64_t count, uint32_t* d_out,
                              uint32_t* d_nerr, void* stream) {
-    if (!count) return 0;
-    if (!d_all || !d_prefix || !d_suffix || !d_out) return fail(-EINVAL, "null argument");
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    const int bs = 256;
-    hipLaunchKernelGGL(crc32c_trim_kernel, dim3((count + bs - 1) / bs), dim3(bs), 0,
-                       static_cast<hipStream_t>(stream), d_all, d_prefix, d_suffix, count, d_out, d_nerr,
-                       pow_table(), rshift_table());
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "crc32c_trim_kernel launch");
+    return trim_batch<Crc32c>(d_all, d_prefix, d_suffix, count, d_out, d_nerr, stream);
 }
 
 int photon_crc32c_extend_device(const void* d_data, uint64_t nbytes, uint32_t seed, uint32_t* d_out, void* stream) {
-    if (!d_out || (!d_data && nbytes)) return fail(-EINVAL, "null buffer or output");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    SmallArgs sa{};
-    uint32_t sgrid = 0;
-    if (small_args(d_data, nbytes, seed, &sa, &sgrid)) {  // <= 256 KiB: the latency path
-        if (int rc = small_image(dev, &sa.image)) return rc;
-        sa.out = d_out;
-        return long_launch(st, sgrid, "crc32c_small_kernel launch", [&](void* state, uint64_t base, uint32_t reset) {
-            sa.acc = static_cast<uint32_t*>(state);
-            sa.tbase = base;
-            sa.treset = reset;
-            hipLaunchKernelGGL((crc32c_small_kernel<kSmallLanes, kSmallRows>), dim3(sgrid), dim3(256), 0, st, sa);
-            return hipGetLastError();
-        });
-    }
-    return pcrc::extend_device_big(dev, d_data, nbytes, seed, d_out, st, cus, 0);
+    return extend_device<Crc32c>(d_data, nbytes, seed, d_out, stream);
 }
 
-}  // extern "C"
-
-namespace pcrc {
-// A span over the small kernel's: the mid layout up to 16 MiB, else the long
-// kernel (tag: as extend_device_long).
-int extend_device_big(int dev, const void* d_data, uint64_t nbytes, uint32_t seed, uint32_t* d_out, hipStream_t st,
-                      int cus, uint32_t tag) {
-    SmallArgs sa{};
-    uint32_t grid = 0;
-    if (!mid_args(d_data, nbytes, seed, &sa, &grid))
-        return extend_device_long(d_data, nbytes, seed, d_out, st, cus, tag);
-    if (int rc = small_image(dev, &sa.image)) return rc;
-    sa.out = d_out;
-    sa.tag = tag;  // slots unset: the tag goes to long_reduce's result word
-    return long_launch(st, grid, "crc32c_small_kernel (mid) launch", [&](void* state, uint64_t base, uint32_t reset) {
-        sa.acc = static_cast<uint32_t*>(state);
-        sa.tbase = base;
-        sa.treset = reset;
-        hipLaunchKernelGGL((crc32c_small_kernel<kMidLanes, kMidRows>), dim3(grid), dim3(256), 0, st, sa);
-        return hipGetLastError();
-    });
-}
-
-// The long kernel for photon_crc32c_extend_device (and, with a tag, for a
-// routed call whose result word lands tagged in pinned memory).
-int extend_device_long(const void* d_data, uint64_t nbytes, uint32_t seed, uint32_t* d_out, hipStream_t st, int cus,
-                       uint32_t tag) {
-    const LongPlan lp = long_plan(d_data, nbytes, cus, false);
-    const LongPowers& pw = long_powers(lp, false);
-    LongArgs a{};
-    long_args(&a, lp, pw, d_data, seed, d_out);
-    a.out_tag = tag;
-    HeavyLaunch heavy(st);
-    return long_launch(st, lp.grid, "crc32c_long_kernel launch", [&](void* state, uint64_t base, uint32_t reset) {
-        a.acc = static_cast<uint32_t*>(state);
-        a.tbase = base;
-        a.treset = reset;
-        if (lp.lanes == 32)
-            hipLaunchKernelGGL((crc32c_long_kernel<32, 4>), dim3(lp.grid), dim3(kBlock), 0, st, a, lane_consts(32));
-        else
-            hipLaunchKernelGGL((crc32c_long_kernel<64, 4>), dim3(lp.grid), dim3(kBlock), 0, st, a, lane_consts(64));
-        return hipGetLastError();
-    });
-}
-
-// photon_crc32c_copy_extend_device: extend_device_long's plan, powers and
-// state with the copying kernel. Every size comes here (the plan's `small`
-// branch serves spans up to 256 KiB).
-int copy_extend_device_long(const void* src, void* d_dst, uint64_t nbytes, uint32_t seed, uint32_t* d_out,
-                            hipStream_t st, int cus) {
-    const LongPlan lp = long_plan(src, nbytes, cus, false);
-    const LongPowers& pw = long_powers(lp, false);
-    CopyLongArgs a{};
-    long_args(&a, lp, pw, src, seed, d_out);
-    a.dst = static_cast<uint8_t*>(d_dst);
-    HeavyLaunch heavy(st);
-    return long_launch(st, lp.grid, "crc32c_copy_long_kernel launch", [&](void* state, uint64_t base, uint32_t reset) {
-        a.acc = static_cast<uint32_t*>(state);
-        a.tbase = base;
-        a.treset = reset;
-        if (lp.lanes == 32)
-            hipLaunchKernelGGL((crc32c_copy_long_kernel<32, 4>), dim3(lp.grid), dim3(kBlock), 0, st, a,
-                               lane_consts(32));
-        else
-            hipLaunchKernelGGL((crc32c_copy_long_kernel<64, 4>), dim3(lp.grid), dim3(kBlock), 0, st, a,
-                               lane_consts(64));
-        return hipGetLastError();
-    });
-}
-}  // namespace pcrc
-
-extern "C" {
 int photon_crc32c_copy_extend_device(const void* src, void* d_dst, uint64_t nbytes, uint32_t seed, uint32_t* d_out,
                                      void* stream) {
-    if (!d_out || ((!src || !d_dst) && nbytes)) return fail(-EINVAL, "null source, destination or output");
-    int cus = 0;
-    int dev = current_device(&cus);
-    if (dev < 0) return dev;
-    return pcrc::copy_extend_device_long(src, d_dst, nbytes, seed, d_out, static_cast<hipStream_t>(stream), cus);
+    return copy_extend_device<Crc32c>(src, d_dst, nbytes, seed, d_out, stream);
 }
 }  // extern "C"
 
@@ -2595,15 +2407,9 @@ namespace {
 std::mutex g_dispatch_mu;
 std::atomic<int> g_dispatch_err{0};
 std::atomic<bool> g_dispatch_on{false};  // written under g_dispatch_mu; read by heavy_mark
-uint32_t (*g_host_crc)(const uint8_t*, size_t, uint32_t) = nullptr;
-uint64_t (*g_host_crc64)(const uint8_t*, size_t, uint64_t) = nullptr;
-void (*g_host_series)(const uint8_t*, uint32_t, uint32_t, uint32_t*) = nullptr;
-uint32_t (*g_host_cseries)(uint32_t*, uint32_t, uint32_t) = nullptr;
-void (*g_host_series64)(const uint8_t*, uint32_t, uint32_t, uint64_t*) = nullptr;
-uint64_t (*g_host_cseries64)(uint64_t*, uint32_t, uint32_t) = nullptr;
 
-// The saved host engines, read by the routed wrappers (written before the
-// routed pointers are published, see photon_crc_set_device_dispatch).
+// The saved host engines (Crc32c::host_crc ..., Crc64::host_cseries), read by
+// the routed wrappers.
 template <typename F>
 F host_engine(F* slot) {
     return __atomic_load_n(slot, __ATOMIC_RELAXED);
@@ -2666,9 +2472,10 @@ void for_host_chunks(const uint8_t* p, size_t n, const char* what, F f) {
     }
 }
 
-uint32_t host_crc_of_device(const uint8_t* p, size_t n, uint32_t crc) {
-    const auto eng = host_engine(&g_host_crc);
-    for_host_chunks(p, n, "crc32c_extend", [&](const uint8_t* h, size_t k) { crc = eng(h, k, crc); });
+template <typename W>
+typename W::T host_crc_of_device(const uint8_t* p, size_t n, typename W::T crc) {
+    const auto eng = host_engine(&W::host_crc);
+    for_host_chunks(p, n, W::kExtend, [&](const uint8_t* h, size_t k) { crc = eng(h, k, crc); });
     return crc;
 }
 
@@ -2823,9 +2630,9 @@ bool scan_until(S& scan, int64_t us) {
 
 // Wait until the `per` tagged words of each of `n` workgroups (slots w[per
 // b + h]) carry `tag`; x[h] = XOR of their low words. `bytes`: the call's
-// payload (the sleep-ahead estimate).
+// payload (the sleep-ahead estimate). kernel + what: the error text.
 int wait_tagged(RoutedStream* r, uint32_t tag, uint32_t n, uint32_t* x, uint32_t per, uint64_t bytes,
-                const char* what) {
+                const char* kernel, const char* what) {
     using clk = std::chrono::steady_clock;
     const volatile uint64_t* w = static_cast<const volatile uint64_t*>(r->h);
     const uint32_t total = n * per;
@@ -2867,31 +2674,35 @@ int wait_tagged(RoutedStream* r, uint32_t tag, uint32_t n, uint32_t* x, uint32_t
             // load), so the words get a grace period before the verdict.
             const hipError_t e = hipStreamSynchronize(r->st);
             if (e == hipSuccess && q == hipSuccess && scan_until(scan, kLandGraceUs)) return 0;
-            return hip_fail(e != hipSuccess ? e : (q != hipSuccess ? q : hipErrorUnknown), what);
+            return hip_fail(e != hipSuccess ? e : (q != hipSuccess ? q : hipErrorUnknown), kernel, what);
         }
     }
 }
 
-int routed_small(int dev, const SmallArgs& sa0, uint32_t sgrid, uint32_t* crc_out) {
+// A small buffer on a routed stream: W::kWords tagged words per workgroup,
+// assembled by W::routed_result.
+template <typename W>
+int routed_small(int dev, const typename W::Small& sa0, uint32_t sgrid, typename W::T* crc_out) {
     RoutedStream* r = nullptr;
     if (int rc = routed_lease(dev, &r)) return rc;
-    SmallArgs sa = sa0;
-    int rc = small_image(dev, &sa.image);
+    typename W::Small sa = sa0;
+    int rc = small_image<W>(dev, &sa.image);
     if (!rc) {
         r->tag = r->tag == 0xffffffffu ? 1u : r->tag + 1u;
         sa.tag = r->tag;
         // the previous call on this stream saw all its slots land: nothing
         // writes them now, and no slot can carry this tag before the launch
-        memset(r->h, 0, 8ull * sgrid);
-        sa.slots = static_cast<uint32_t*>(r->d);
-        hipLaunchKernelGGL((crc32c_small_kernel<kSmallLanes, kSmallRows>), dim3(sgrid), dim3(256), 0, r->st, sa);
+        memset(r->h, 0, 8ull * W::kWords * sgrid);
+        sa.slots = static_cast<decltype(sa.slots)>(r->d);
+        hipLaunchKernelGGL((W::template small_kernel<kSmallLanes, kSmallRows>()), dim3(sgrid), dim3(256), 0, r->st,
+                           sa);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = hip_fail(e, "crc32c_small_kernel launch");
+        if (e != hipSuccess) rc = hip_fail(e, W::kKernel, "_small_kernel launch");
     }
     if (!rc) {
-        uint32_t x = 0;
-        rc = wait_tagged(r, sa.tag, sgrid, &x, 1, sa.eoff, "crc32c_small_kernel (routed)");
-        if (!rc) *crc_out = x;
+        uint32_t x[2] = {0, 0};
+        rc = wait_tagged(r, sa.tag, sgrid, x, W::kWords, sa.eoff, W::kKernel, "_small_kernel (routed)");
+        if (!rc) *crc_out = W::routed_result(x, /*raw=*/true);
     } else {
         (void)hipStreamSynchronize(r->st);  // nothing left running on a returned stream
     }
@@ -2899,9 +2710,10 @@ int routed_small(int dev, const SmallArgs& sa0, uint32_t sgrid, uint32_t* crc_ou
     return rc;
 }
 
-// A long buffer on a routed stream: the last workgroup's tagged result word
-// (long_reduce) is spun on like the small kernels' words.
-int routed_long(int dev, const uint8_t* p, uint64_t n, uint32_t crc, uint32_t* crc_out) {
+// A long buffer on a routed stream: the last workgroup's tagged result words
+// (long_reduce) are spun on like the small kernels' words.
+template <typename W>
+int routed_long(int dev, const uint8_t* p, uint64_t n, typename W::T crc, typename W::T* crc_out) {
     RoutedStream* r = nullptr;
     if (int rc = routed_lease(dev, &r)) return rc;
     int cus = 0;
@@ -2910,78 +2722,19 @@ int routed_long(int dev, const uint8_t* p, uint64_t n, uint32_t crc, uint32_t* c
     if (!rc) {
         r->tag = r->tag == 0xffffffffu ? 1u : r->tag + 1u;
         tag = r->tag;
-        memset(r->h, 0, 8);
-        rc = extend_device_big(dev, p, n, crc, static_cast<uint32_t*>(r->d), r->st, cus, tag);
+        memset(r->h, 0, 8 * W::kWords);
+        rc = extend_device_big<W>(dev, p, n, crc, static_cast<typename W::T*>(r->d), r->st, cus, tag);
     }
     if (!rc) {
-        uint32_t x = 0;
-        rc = wait_tagged(r, tag, 1, &x, 1, n, "crc32c mid/long kernel (routed)");
+        uint32_t x[2] = {0, 0};
+        rc = wait_tagged(r, tag, 1, x, W::kWords, n, W::kKernel, " mid/long kernel (routed)");
         if (!rc) {
-            *crc_out = x;
+            *crc_out = W::routed_result(x, /*raw=*/false);
         } else {
-            const volatile uint64_t* w = static_cast<const volatile uint64_t*>(r->h);
-            char buf[96];
-            snprintf(buf, sizeof buf, "; word %016llx, tag %08x", (unsigned long long)w[0], tag);
-            g_err += buf + long_state_diag(r->st);
-        }
-    } else {
-        (void)hipStreamSynchronize(r->st);
-    }
-    routed_return(r);
-    return rc;
-}
-
-// routed_long for CRC-64: the result as two tagged words.
-int routed_long64(int dev, const uint8_t* p, uint64_t n, uint64_t crc, uint64_t* crc_out) {
-    RoutedStream* r = nullptr;
-    if (int rc = routed_lease(dev, &r)) return rc;
-    int cus = 0;
-    int rc = current_device(&cus) < 0 ? -ENODEV : 0;
-    uint32_t tag = 0;
-    if (!rc) {
-        r->tag = r->tag == 0xffffffffu ? 1u : r->tag + 1u;
-        tag = r->tag;
-        memset(r->h, 0, 16);
-        rc = extend64_device_big(dev, p, n, crc, static_cast<uint64_t*>(r->d), r->st, cus, tag);
-    }
-    if (!rc) {
-        uint32_t x[2] = {0, 0};
-        rc = wait_tagged(r, tag, 1, x, 2, n, "crc64 mid/long kernel (routed)");
-        if (rc) {
-            const volatile uint64_t* w = static_cast<const volatile uint64_t*>(r->h);
             char buf[128];
-            snprintf(buf, sizeof buf, "; words %016llx %016llx, tag %08x", (unsigned long long)w[0],
-                     (unsigned long long)w[1], tag);
+            W::routed_diag(buf, sizeof buf, static_cast<const volatile uint64_t*>(r->h), tag);
             g_err += buf + long_state_diag(r->st);
         }
-        if (!rc) *crc_out = ((uint64_t)x[1] << 32) | x[0];  // long_reduce already inverted it
-    } else {
-        (void)hipStreamSynchronize(r->st);
-    }
-    routed_return(r);
-    return rc;
-}
-
-// CRC-64 small buffers on a routed stream: the workgroups' raw values come
-// back as two tagged words each; the host XORs and inverts (crc.cpp:119-122).
-int routed_small64(int dev, const Small64Args& sa0, uint32_t sgrid, uint64_t* crc_out) {
-    RoutedStream* r = nullptr;
-    if (int rc = routed_lease(dev, &r)) return rc;
-    Small64Args sa = sa0;
-    int rc = small64_image(dev, &sa.image);
-    if (!rc) {
-        r->tag = r->tag == 0xffffffffu ? 1u : r->tag + 1u;
-        sa.tag = r->tag;
-        sa.slots = static_cast<uint64_t*>(r->d);
-        memset(r->h, 0, 16ull * sgrid);  // as routed_small
-        hipLaunchKernelGGL((crc64_small_kernel<kSmallLanes, kSmallRows>), dim3(sgrid), dim3(256), 0, r->st, sa);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = hip_fail(e, "crc64_small_kernel launch");
-    }
-    if (!rc) {
-        uint32_t x[2] = {0, 0};
-        rc = wait_tagged(r, sa.tag, sgrid, x, 2, sa.eoff, "crc64_small_kernel (routed)");
-        if (!rc) *crc_out = ~(((uint64_t)x[1] << 32) | x[0]);
     } else {
         (void)hipStreamSynchronize(r->st);
     }
@@ -2995,7 +2748,7 @@ int routed_small64(int dev, const Small64Args& sa0, uint32_t sgrid, uint64_t* cr
 // started by the first routed call of its width: a non-blocking stream, the
 // doorbell, the pinned slot area, the last seq posted. One call at a time
 // uses a service (try-lock: a call that finds it busy, or not running, takes
-// the launch path, routed_small / routed_small64); the first call after it
+// the launch path, routed_small); the first call after it
 // ended starts a new launch and is its first request.
 struct SmallService {
     std::mutex mu;
@@ -3260,8 +3013,8 @@ bool heavy_in_flight(int dev) {
 
 // Serve one routed small call through the service of its width: 0 = the
 // slots' XOR is in x[0] (CRC-64: x[1] the high words), 1 = not served (take
-// the launch path). The request: a0, nb, s0, k, wg0, eoff as small_args /
-// small64_args computed them, seed (CRC-64: the inverted init).
+// the launch path). The request: a0, nb, s0, k, wg0, eoff as small_args
+// computed them, seed (W::seed_word; CRC-64: the inverted init).
 int service_small(int dev, int kind, const uint8_t* a0, uint32_t nb, uint32_t s0, uint32_t k, uint32_t wg0,
                   uint32_t eoff, uint64_t seed, uint32_t x[2]) {
     const int idle_us = g_svc_idle_us.load(std::memory_order_relaxed);
@@ -3283,11 +3036,11 @@ int service_small(int dev, int kind, const uint8_t* a0, uint32_t nb, uint32_t s0
         const void* img = nullptr;
         if (kind == 0) {
             const uint32_t* i32 = nullptr;
-            if (small_image(dev, &i32)) return 1;
+            if (small_image<Crc32c>(dev, &i32)) return 1;
             img = i32;
         } else {
             const uint64_t* i64 = nullptr;
-            if (small64_image(dev, &i64)) return 1;
+            if (small_image<Crc64>(dev, &i64)) return 1;
             img = i64;
         }
         // this launch's doorbell; its request words carry the last seq posted
@@ -3367,41 +3120,39 @@ int service_small(int dev, int kind, const uint8_t* a0, uint32_t nb, uint32_t s0
     return 0;
 }
 
-uint32_t dispatch_crc(const uint8_t* p, size_t n, uint32_t crc) {
+// The routed crc32c_extend / crc64ecma_extend.
+template <typename W>
+typename W::T dispatch_crc(const uint8_t* p, size_t n, typename W::T crc) {
     const int dev = n ? device_of(p) : -1;
-    if (dev < 0) return host_engine(&g_host_crc)(p, n, crc);
+    if (dev < 0) return host_engine(&W::host_crc)(p, n, crc);
     DeviceScope scope(dev);
-    uint32_t r = 0;
-    SmallArgs sa{};
+    typename W::T r = 0;
+    typename W::Small sa{};
     uint32_t sgrid = 0;
     int rc;
     uint32_t x[2];
-    if (small_args(p, n, crc, &sa, &sgrid, kSvcMaxBlocks) &&
-        service_small(dev, 0, sa.a0, sa.nb, sa.s0, sa.k, sa.wg0, sa.eoff, sa.seed, x) == 0) {
-        r = x[0];  // per-workgroup words in pinned memory, XORed by service_small
+    if (small_args<W>(p, n, crc, &sa, &sgrid, kSvcMaxBlocks) &&
+        service_small(dev, W::kService, sa.a0, sa.nb, sa.s0, sa.k, sa.wg0, sa.eoff, W::seed_word(sa), x) == 0) {
+        r = W::routed_result(x, /*raw=*/true);  // per-workgroup words in pinned memory, XORed by service_small
         rc = 0;
     } else if (sa.nb && sa.nb <= kSmallBlocks) {
-        rc = routed_small(dev, sa, sgrid, &r);
+        rc = routed_small<W>(dev, sa, sgrid, &r);
     } else {
-        rc = routed_long(dev, p, n, crc, &r);
+        rc = routed_long<W>(dev, p, n, crc, &r);
     }
     if (!rc) return r;
-    routed_failure("crc32c_extend", rc);
-    return host_crc_of_device(p, n, crc);
+    routed_failure(W::kExtend, rc);
+    return host_crc_of_device<W>(p, n, crc);
 }
 
-void dispatch_series(const uint8_t* buf, uint32_t part, uint32_t n, uint32_t* parts) {
+// The routed crc32c_series / crc64ecma_series: run(out, stream) enqueues the
+// device form.
+template <typename W, typename R>
+void dispatch_series_with(const uint8_t* buf, uint32_t part, uint32_t n, typename W::T* parts, R run) {
+    typedef typename W::T T;
     const int dev = (part && n) ? device_of(buf) : -1;
-    if (dev < 0) return host_engine(&g_host_series)(buf, part, n, parts);
+    if (dev < 0) return host_engine(&W::host_series)(buf, part, n, parts);
     DeviceScope scope(dev);
-    // The device form keeps the SSE4.2 engine's rule (parts < 8 B give 0,
-    // crc.cpp:481-500); when the saved host engine is crc32c_series_sw those
-    // parts get their real CRCs (crc.cpp:474-478), so run the plain batch.
-    const bool sw = host_engine(&g_host_series) == crc32c_series_sw;
-    auto run = [&](uint32_t* out, hipStream_t st) {
-        return sw ? photon_crc32c_batch_strided(buf, part, part, n, 0, nullptr, out, st)
-                  : photon_crc32c_series_device(buf, part, n, out, st);
-    };
     const bool parts_on_dev = device_of(parts) == dev;
     int rc;
     if (parts_on_dev) {
@@ -3414,129 +3165,68 @@ void dispatch_series(const uint8_t* buf, uint32_t part, uint32_t n, uint32_t* pa
             routed_return(r);
         }
     } else {
-        rc = with_scratch(dev, 4ull * n, parts, 4ull * n,
-                          [&](void* d, hipStream_t st) { return run(static_cast<uint32_t*>(d), st); });
+        rc = with_scratch(dev, sizeof(T) * n, parts, sizeof(T) * n,
+                          [&](void* d, hipStream_t st) { return run(static_cast<T*>(d), st); });
     }
     if (!rc) return;
-    routed_failure("crc32c_series", rc);
-    std::vector<uint32_t> h(n);
+    routed_failure(W::kSeries, rc);
+    std::vector<T> h(n);
     uint64_t i = 0;
     std::vector<uint8_t> part_buf;
-    for_host_chunks(buf, (size_t)part * n, "crc32c_series", [&](const uint8_t* hp, size_t k) {
+    for_host_chunks(buf, (size_t)part * n, W::kSeries, [&](const uint8_t* hp, size_t k) {
         // whole parts only: gather across chunk edges into part_buf
         part_buf.insert(part_buf.end(), hp, hp + k);
         size_t whole = part_buf.size() / part;
-        host_engine(&g_host_series)(part_buf.data(), part, (uint32_t)whole, h.data() + i);
+        host_engine(&W::host_series)(part_buf.data(), part, (uint32_t)whole, h.data() + i);
         i += whole;
         part_buf.erase(part_buf.begin(), part_buf.begin() + whole * part);
     });
     if (parts_on_dev) {
-        hipError_t e = hipMemcpy(parts, h.data(), 4ull * n, hipMemcpyHostToDevice);
-        if (e != hipSuccess) routed_abort("crc32c_series", e);
+        hipError_t e = hipMemcpy(parts, h.data(), sizeof(T) * n, hipMemcpyHostToDevice);
+        if (e != hipSuccess) routed_abort(W::kSeries, e);
     } else {
-        memcpy(parts, h.data(), 4ull * n);
+        memcpy(parts, h.data(), sizeof(T) * n);
     }
 }
 
-uint32_t dispatch_combine_series(uint32_t* crc, uint32_t part, uint32_t n) {
-    const int dev = n ? device_of(crc) : -1;
-    if (dev < 0) return host_engine(&g_host_cseries)(crc, part, n);
-    DeviceScope scope(dev);
-    uint32_t r = 0;  // device scratch, not the pinned word: the kernel accumulates with device atomics
-    int rc = with_scratch(dev, 4, &r, 4, [&](void* d, hipStream_t st) {
-        return photon_crc32c_combine_series_device(crc, part, n, static_cast<uint32_t*>(d), st);
+void dispatch_series(const uint8_t* buf, uint32_t part, uint32_t n, uint32_t* parts) {
+    // The device form keeps the SSE4.2 engine's rule (parts < 8 B give 0,
+    // crc.cpp:481-500); when the saved host engine is crc32c_series_sw those
+    // parts get their real CRCs (crc.cpp:474-478), so run the plain batch.
+    dispatch_series_with<Crc32c>(buf, part, n, parts, [&](uint32_t* out, hipStream_t st) {
+        return host_engine(&Crc32c::host_series) == crc32c_series_sw
+                   ? photon_crc32c_batch_strided(buf, part, part, n, 0, nullptr, out, st)
+                   : photon_crc32c_series_device(buf, part, n, out, st);
     });
-    if (!rc) return r;
-    routed_failure("crc32c_combine_series", rc);
-    std::vector<uint32_t> h(n);
-    hipError_t e = hipMemcpy(h.data(), crc, 4ull * n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) routed_abort("crc32c_combine_series", e);
-    return host_engine(&g_host_cseries)(h.data(), part, n);
 }
 
-uint64_t dispatch_crc64(const uint8_t* p, size_t n, uint64_t crc) {
-    const int dev = n ? device_of(p) : -1;
-    if (dev < 0) return host_engine(&g_host_crc64)(p, n, crc);
-    DeviceScope scope(dev);
-    uint64_t r = 0;
-    Small64Args sa{};
-    uint32_t sgrid = 0;
-    int rc;
-    uint32_t x[2];
-    if (small64_args(p, n, crc, &sa, &sgrid, kSvcMaxBlocks) &&
-        service_small(dev, 1, sa.a0, sa.nb, sa.s0, sa.k, sa.wg0, sa.eoff, sa.init, x) == 0) {
-        r = ~(((uint64_t)x[1] << 32) | x[0]);  // as routed_small64: XOR of the raw values, inverted
-        rc = 0;
-    } else if (sa.nb && sa.nb <= kSmallBlocks) {
-        rc = routed_small64(dev, sa, sgrid, &r);
-    } else {
-        rc = routed_long64(dev, p, n, crc, &r);
-    }
-    if (!rc) return r;
-    routed_failure("crc64ecma_extend", rc);
-    const auto eng = host_engine(&g_host_crc64);
-    for_host_chunks(p, n, "crc64ecma_extend", [&](const uint8_t* h, size_t k) { crc = eng(h, k, crc); });
-    return crc;
-}
-
-// dispatch_series / dispatch_combine_series for CRC-64/ECMA. The host engines
-// have no part_size quirk (crc64_cpu.cpp), so there is no engine to select.
+// The host engines have no part_size quirk (crc64_cpu.cpp), so there is no
+// engine to select.
 void dispatch_series64(const uint8_t* buf, uint32_t part, uint32_t n, uint64_t* parts) {
-    const int dev = (part && n) ? device_of(buf) : -1;
-    if (dev < 0) return host_engine(&g_host_series64)(buf, part, n, parts);
-    DeviceScope scope(dev);
-    const bool parts_on_dev = device_of(parts) == dev;
-    int rc;
-    if (parts_on_dev) {
-        RoutedStream* r = nullptr;
-        rc = routed_lease(dev, &r);
-        if (!rc) {
-            rc = photon_crc64ecma_series_device(buf, part, n, parts, r->st);
-            hipError_t e = hipStreamSynchronize(r->st);
-            if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
-            routed_return(r);
-        }
-    } else {
-        rc = with_scratch(dev, 8ull * n, parts, 8ull * n, [&](void* d, hipStream_t st) {
-            return photon_crc64ecma_series_device(buf, part, n, static_cast<uint64_t*>(d), st);
-        });
-    }
-    if (!rc) return;
-    routed_failure("crc64ecma_series", rc);
-    std::vector<uint64_t> h(n);
-    uint64_t i = 0;
-    std::vector<uint8_t> part_buf;
-    for_host_chunks(buf, (size_t)part * n, "crc64ecma_series", [&](const uint8_t* hp, size_t k) {
-        // whole parts only: gather across chunk edges into part_buf
-        part_buf.insert(part_buf.end(), hp, hp + k);
-        size_t whole = part_buf.size() / part;
-        host_engine(&g_host_series64)(part_buf.data(), part, (uint32_t)whole, h.data() + i);
-        i += whole;
-        part_buf.erase(part_buf.begin(), part_buf.begin() + whole * part);
+    dispatch_series_with<Crc64>(buf, part, n, parts, [&](uint64_t* out, hipStream_t st) {
+        return photon_crc64ecma_series_device(buf, part, n, out, st);
     });
-    if (parts_on_dev) {
-        hipError_t e = hipMemcpy(parts, h.data(), 8ull * n, hipMemcpyHostToDevice);
-        if (e != hipSuccess) routed_abort("crc64ecma_series", e);
-    } else {
-        memcpy(parts, h.data(), 8ull * n);
-    }
 }
 
-uint64_t dispatch_combine_series64(uint64_t* crc, uint32_t part, uint32_t n) {
+// The routed crc32c_combine_series / crc64ecma_combine_series.
+template <typename W>
+typename W::T dispatch_combine_series(typename W::T* crc, uint32_t part, uint32_t n) {
+    typedef typename W::T T;
     const int dev = n ? device_of(crc) : -1;
-    if (dev < 0) return host_engine(&g_host_cseries64)(crc, part, n);
+    if (dev < 0) return host_engine(&W::host_cseries)(crc, part, n);
     DeviceScope scope(dev);
-    uint64_t r = 0;  // device scratch, as dispatch_combine_series: the kernel accumulates with device atomics
-    int rc = with_scratch(dev, 8, &r, 8, [&](void* d, hipStream_t st) {
-        return photon_crc64ecma_combine_series_device(crc, part, n, static_cast<uint64_t*>(d), st);
+    T r = 0;  // device scratch, not the pinned word: the kernel accumulates with device atomics
+    int rc = with_scratch(dev, sizeof(T), &r, sizeof(T), [&](void* d, hipStream_t st) {
+        return combine_series_device<W>(crc, part, n, static_cast<T*>(d), st);
     });
     if (!rc) return r;
-    routed_failure("crc64ecma_combine_series", rc);
-    std::vector<uint64_t> h(n);
-    hipError_t e = hipMemcpy(h.data(), crc, 8ull * n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) routed_abort("crc64ecma_combine_series", e);
-    return host_engine(&g_host_cseries64)(h.data(), part, n);
+    routed_failure(W::kCombineSeries, rc);
+    std::vector<T> h(n);
+    hipError_t e = hipMemcpy(h.data(), crc, sizeof(T) * n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) routed_abort(W::kCombineSeries, e);
+    return host_engine(&W::host_cseries)(h.data(), part, n);
 }
+
 
 }  // namespace
 }  // namespace pcrc
@@ -3555,29 +3245,30 @@ extern "C" int photon_crc_set_device_dispatch(int on) {
     using namespace pcrc;
     std::lock_guard<std::mutex> lk(g_dispatch_mu);
     if (on && !g_dispatch_on) {
-        __atomic_store_n(&g_host_crc, __atomic_load_n(&crc32c_auto, __ATOMIC_ACQUIRE), __ATOMIC_RELAXED);
-        __atomic_store_n(&g_host_series, __atomic_load_n(&crc32c_series_auto, __ATOMIC_ACQUIRE), __ATOMIC_RELAXED);
-        __atomic_store_n(&g_host_cseries, __atomic_load_n(&crc32c_combine_series_auto, __ATOMIC_ACQUIRE),
+        __atomic_store_n(&Crc32c::host_crc, __atomic_load_n(&crc32c_auto, __ATOMIC_ACQUIRE), __ATOMIC_RELAXED);
+        __atomic_store_n(&Crc32c::host_series, __atomic_load_n(&crc32c_series_auto, __ATOMIC_ACQUIRE),
                          __ATOMIC_RELAXED);
-        __atomic_store_n(&g_host_crc64, __atomic_load_n(&crc64ecma_auto, __ATOMIC_ACQUIRE), __ATOMIC_RELAXED);
-        __atomic_store_n(&g_host_series64, __atomic_load_n(&crc64ecma_series_auto, __ATOMIC_ACQUIRE),
+        __atomic_store_n(&Crc32c::host_cseries, __atomic_load_n(&crc32c_combine_series_auto, __ATOMIC_ACQUIRE),
                          __ATOMIC_RELAXED);
-        __atomic_store_n(&g_host_cseries64, __atomic_load_n(&crc64ecma_combine_series_auto, __ATOMIC_ACQUIRE),
+        __atomic_store_n(&Crc64::host_crc, __atomic_load_n(&crc64ecma_auto, __ATOMIC_ACQUIRE), __ATOMIC_RELAXED);
+        __atomic_store_n(&Crc64::host_series, __atomic_load_n(&crc64ecma_series_auto, __ATOMIC_ACQUIRE),
                          __ATOMIC_RELAXED);
-        __atomic_store_n(&crc32c_auto, &dispatch_crc, __ATOMIC_RELEASE);
+        __atomic_store_n(&Crc64::host_cseries, __atomic_load_n(&crc64ecma_combine_series_auto, __ATOMIC_ACQUIRE),
+                         __ATOMIC_RELAXED);
+        __atomic_store_n(&crc32c_auto, &dispatch_crc<Crc32c>, __ATOMIC_RELEASE);
         __atomic_store_n(&crc32c_series_auto, &dispatch_series, __ATOMIC_RELEASE);
-        __atomic_store_n(&crc32c_combine_series_auto, &dispatch_combine_series, __ATOMIC_RELEASE);
-        __atomic_store_n(&crc64ecma_auto, &dispatch_crc64, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc32c_combine_series_auto, &dispatch_combine_series<Crc32c>, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc64ecma_auto, &dispatch_crc<Crc64>, __ATOMIC_RELEASE);
         __atomic_store_n(&crc64ecma_series_auto, &dispatch_series64, __ATOMIC_RELEASE);
-        __atomic_store_n(&crc64ecma_combine_series_auto, &dispatch_combine_series64, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc64ecma_combine_series_auto, &dispatch_combine_series<Crc64>, __ATOMIC_RELEASE);
         g_dispatch_on = true;
     } else if (!on && g_dispatch_on) {
-        __atomic_store_n(&crc32c_auto, g_host_crc, __ATOMIC_RELEASE);
-        __atomic_store_n(&crc32c_series_auto, g_host_series, __ATOMIC_RELEASE);
-        __atomic_store_n(&crc32c_combine_series_auto, g_host_cseries, __ATOMIC_RELEASE);
-        __atomic_store_n(&crc64ecma_auto, g_host_crc64, __ATOMIC_RELEASE);
-        __atomic_store_n(&crc64ecma_series_auto, g_host_series64, __ATOMIC_RELEASE);
-        __atomic_store_n(&crc64ecma_combine_series_auto, g_host_cseries64, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc32c_auto, Crc32c::host_crc, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc32c_series_auto, Crc32c::host_series, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc32c_combine_series_auto, Crc32c::host_cseries, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc64ecma_auto, Crc64::host_crc, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc64ecma_series_auto, Crc64::host_series, __ATOMIC_RELEASE);
+        __atomic_store_n(&crc64ecma_combine_series_auto, Crc64::host_cseries, __ATOMIC_RELEASE);
         g_dispatch_on = false;
     }
     return g_dispatch_err.exchange(0) ? -EIO : 0;
