@@ -302,6 +302,61 @@ int photon_crc32c_extend_device(const void* d_data, uint64_t nbytes, uint32_t se
 int photon_crc32c_copy_extend_device(const void* src, void* d_dst, uint64_t nbytes,
                                      uint32_t seed, uint32_t* d_out, void* stream);
 
+/* Copy + CRC-32C of MANY large parts in ONE pass over the whole device: the
+ * middle between the batch calls at (iv) (one lane group per buffer: right
+ * for 64 Ki x 64 KiB, wrong for 256 x 16 MiB) and a loop of
+ * photon_crc32c_copy_extend_device (one launch per part, whose fixed cost
+ * dominates parts of a few MiB). The descriptors are device-resident, as in
+ * photon_crc32c_copy_batch_iov: part i is d_src[i] = {base, len} and lands at
+ * d_dst[i]. max_part_bytes caps every part, n_i = min(d_src[i].len,
+ * max_part_bytes) (a cap like d_size in photon_crc32c_copy_msg_iov_n, and all
+ * the host knows of the lengths): [d_dst[i], d_dst[i] + n_i) receives the
+ * first n_i bytes of part i, and
+ *     d_out[i] = crc32c_extend(src_i, n_i, seed_i),
+ * seed_i = d_seeds ? d_seeds[i] : seed0, bit-identical to
+ * photon_crc32c_copy_extend_device / photon_crc32c_extend_device on the same
+ * bytes. Every part is cut into pieces (32 KiB unless
+ * photon_crc_set_parts_piece says otherwise) anchored at a 4 KiB boundary of
+ * its source, one lane group per piece over a persistent grid; a second
+ * kernel folds each part's piece CRCs with its seed. Two launches per call.
+ * Contract (iv) holds: sources are HBM, or pinned / registered host memory
+ * read in place; destinations are device-accessible; no source overlaps a
+ * destination and no two destinations overlap (the caller's responsibility,
+ * not checked); no byte outside a destination range is written and nothing
+ * is read-modify-written, so parts may land back to back at odd addresses;
+ * any alignment is correct; a part with (d_dst[i] - base_i) % 16 == 0 is read
+ * exactly once, any other is copied piece by piece first and checksummed
+ * from the cache. d_work is the call's workspace of at least
+ * photon_crc_parts_work_bytes(nparts, max_part_bytes, 0) bytes of device
+ * memory (one CRC word per piece slot), 8-byte aligned; it needs no clearing
+ * and holds nothing between calls. Asynchronous on `stream`; the calls
+ * allocate nothing, synchronise nothing and use plain stores only (no
+ * atomics, no memset, no per-stream state), so a call is capturable into a
+ * graph and replayable any number of times, and calls may run concurrently
+ * with distinct d_out / d_work. No CPU fallback.
+ *   - nparts == 0 returns 0 and touches nothing.
+ *   - A part with n_i == 0 writes its seed to d_out[i] and nothing else (its
+ *     base may be null); max_part_bytes == 0 makes every part empty.
+ *   - A null d_src / d_iov, d_out or d_work, or a null d_dst in the copying
+ *     forms, with nparts > 0 gives -EINVAL ("null ..."); work_bytes below
+ *     photon_crc_parts_work_bytes(...) gives -EINVAL naming both numbers; more
+ *     than 2^40 piece slots (nparts x slots per part) gives -EINVAL.
+ * The object's CRC is ONE photon_crc32c_fold_parts_n call over d_out on the
+ * same stream (below), as after the per-part loop. */
+int photon_crc32c_copy_parts_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts,
+                               uint64_t max_part_bytes, uint32_t seed0, const uint32_t* d_seeds,
+                               uint32_t* d_out, void* d_work, uint64_t work_bytes, void* stream);
+/* The same without the copy: d_out[i] = crc32c_extend(d_iov[i].base, n_i,
+ * seed_i), every part cut over the chip (photon_crc32c_batch_iov gives a part
+ * to one lane group). */
+int photon_crc32c_batch_parts_n(const photon_crc_iovec* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                                uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_out,
+                                void* d_work, uint64_t work_bytes, void* stream);
+/* Bytes of d_work the four _parts_n calls need for these arguments under the
+ * current piece setting: nparts x max(1, ceil(max_part_bytes / piece)) words
+ * of 4 bytes, or 8 if crc64 (~0 when that is more than 2^40 words). */
+uint64_t photon_crc_parts_work_bytes(uint64_t nparts, uint64_t max_part_bytes, int crc64);
+
 /* (many GPUs) ONE logical buffer whose bytes lie on several devices of this
  * process: span i = [d_data, d_data + nbytes) on `device`, the spans in
  * buffer order. Every span runs photon_crc32c_extend_device (from seed 0) on
@@ -445,6 +500,18 @@ int photon_crc64ecma_extend_device(const void* d_data, uint64_t nbytes, uint64_t
  * photon_crc64ecma_fold_parts_n call on the same stream (below). */
 int photon_crc64ecma_copy_extend_device(const void* src, void* d_dst, uint64_t nbytes,
                                         uint64_t seed, uint64_t* d_out, void* stream);
+/* photon_crc32c_copy_parts_n / photon_crc32c_batch_parts_n for CRC-64/ECMA:
+ * the same arguments, cut, workspace rule (photon_crc_parts_work_bytes(...,
+ * 1): 8-byte words) and contract; d_out[i] = crc64ecma_extend(src_i, n_i,
+ * seed_i). The parts of an OSS multipart upload are landed and given their
+ * x-oss-hash-crc64ecma by one call; the object's CRC is one
+ * photon_crc64ecma_fold_parts_n call on the same stream. */
+int photon_crc64ecma_copy_parts_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts,
+                                  uint64_t max_part_bytes, uint64_t seed0, const uint64_t* d_seeds,
+                                  uint64_t* d_out, void* d_work, uint64_t work_bytes, void* stream);
+int photon_crc64ecma_batch_parts_n(const photon_crc_iovec* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                                   uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out,
+                                   void* d_work, uint64_t work_bytes, void* stream);
 /* photon_crc32c_extend_spans for CRC-64/ECMA (crc64ecma_combine's identity:
  * the inverted CRC folds the same way). */
 int photon_crc64ecma_extend_spans(const photon_crc_span* spans, int nspans, uint64_t seed, uint64_t* h_result);

@@ -160,6 +160,31 @@ int photon_crc_test_tables(int which, uint32_t* out, int n);
 int photon_crc_test_long_plan(uint64_t addr, uint64_t n, int cus, int lanes, int rounds, int crc64, uint64_t* out,
                               int nout);
 
+/* Piece size of photon_crc32c_copy_parts_n / photon_crc32c_batch_parts_n and
+ * the CRC-64 forms (testing / tuning): 0 = automatic (32 KiB, DESIGN.md
+ * §4.9), else a multiple of 4 KiB from 4 KiB to 1 GiB. It sets the slots per
+ * part and so photon_crc_parts_work_bytes: size the workspace after setting
+ * it. The lane-group size follows the piece size by the batch kernels' rule. */
+int photon_crc_set_parts_piece(uint64_t bytes);
+
+/* The cut of ONE part of `len` bytes at address `addr` (not dereferenced)
+ * under the cap max_part_bytes, in pieces of `piece` bytes (0 = the current
+ * setting), exactly as the piece kernels derive it
+ * (photonlibos_amd/csrc/parts_plan.h): out[0] = P (the slots the task space
+ * gives every part), out[1] = the pieces, then (offset, length) per piece in
+ * slot order, empty slots left out. Returns the words written, or -EINVAL
+ * (bad piece, or cap words too few). */
+int photon_crc_test_parts_plan(uint64_t addr, uint64_t len, uint64_t max_part_bytes, uint64_t piece, uint64_t* out,
+                               int cap);
+
+/* Bench utility (scripts/bench_copy_crc.py --parts): the SECOND launch of a
+ * photon_crc32c_copy_parts_n / photon_crc64ecma_copy_parts_n call alone -- the
+ * part fold kernel over the workspace d_work that such a call with the same
+ * d_src, nparts, max_part_bytes and piece setting left -- so its time can be
+ * reported apart. d_seeds / d_out are uint32_t words, or uint64_t if crc64. */
+int photon_crc_util_parts_fold(int crc64, const void* d_src, uint64_t nparts, uint64_t max_part_bytes,
+                               uint64_t seed0, const void* d_seeds, void* d_out, const void* d_work, void* stream);
+
 /* CPU replay of the fold_parts kernels (photon_crc32c_fold_parts_n /
  * photon_crc64ecma_fold_parts_n; photonlibos_amd/csrc/fold_parts.h): the
  * kernels' per-thread run step and combine step, run on the host for a

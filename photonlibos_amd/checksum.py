@@ -33,6 +33,8 @@ __all__ = [
     "copy_msg_iov_n", "copy_msg64_iov_n",
     "copy_msg_iov_seg_n", "copy_msg64_iov_seg_n", "SEG_OF_SRC", "SEG_OF_DST",
     "copy_extend_device", "copy_extend64_device",
+    "copy_parts_device", "copy_parts64_device", "batch_parts_device", "batch_parts64_device", "parts_work_bytes",
+    "set_parts_piece",
     "series64_device", "combine_series64_device", "fold_parts_device", "fold_parts64_device",
     "crc64ecma_series_at", "crc64ecma_combine_series_at",
     "batch64_strided", "batch64_iov", "combine64_batch", "trim64_batch", "batch64_msg_n", "host_batch64_strided", "extend64_device", "extend_spans", "extend64_spans", "Span", "combine_batch", "fill_splitmix", "read_stream", "IOVEC_DTYPE",
@@ -514,6 +516,57 @@ def copy_extend64_device(src, dst, nbytes, out, seed=0, stream=None):
     """copy_extend_device for CRC-64/ECMA: *out = crc64ecma_extend(src, nbytes, seed). Async."""
     _check(lib().photon_crc64ecma_copy_extend_device(_ptr(src), _ptr(dst), nbytes, seed & 0xFFFFFFFFFFFFFFFF,
                                                      _ptr(out), _stream(stream)))
+
+
+def parts_work_bytes(nparts, max_part_bytes, crc64=False):
+    """Bytes of workspace copy_parts*_device / batch_parts*_device need for these arguments under
+    the current piece setting (set_parts_piece)."""
+    return lib().photon_crc_parts_work_bytes(nparts, max_part_bytes, int(bool(crc64)))
+
+
+def set_parts_piece(nbytes):
+    """Piece size of the parts calls: 0 = automatic (32 KiB), else a multiple of 4 KiB (tuning.h)."""
+    _check(lib().photon_crc_set_parts_piece(nbytes))
+
+
+def _work_bytes(work, work_bytes):
+    if work_bytes is not None:
+        return work_bytes
+    return work.numel() * work.element_size() if hasattr(work, "numel") else 0
+
+
+def copy_parts_device(src_iov, dst_ptrs, nparts, max_part_bytes, out, work, work_bytes=None, seed=0, seeds=None,
+                      stream=None):
+    """Copy + CRC-32C of many large parts in one pass over the whole device: dst_ptrs[i] receives the
+    first n_i = min(src_iov[i].len, max_part_bytes) bytes of part i and out[i] = crc32c_extend over them
+    from seeds[i] or seed, what copy_extend_device gives per part. work: device workspace of at least
+    parts_work_bytes(nparts, max_part_bytes) bytes (work_bytes, or the tensor's size). Async, capturable."""
+    _check(lib().photon_crc32c_copy_parts_n(_ptr(src_iov), _ptr(dst_ptrs), nparts, max_part_bytes,
+                                            seed & 0xFFFFFFFF, _ptr(seeds), _ptr(out), _ptr(work),
+                                            _work_bytes(work, work_bytes), _stream(stream)))
+
+
+def copy_parts64_device(src_iov, dst_ptrs, nparts, max_part_bytes, out, work, work_bytes=None, seed=0, seeds=None,
+                        stream=None):
+    """copy_parts_device for CRC-64/ECMA (uint64 seeds / out; parts_work_bytes(..., crc64=True))."""
+    _check(lib().photon_crc64ecma_copy_parts_n(_ptr(src_iov), _ptr(dst_ptrs), nparts, max_part_bytes,
+                                               seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(out), _ptr(work),
+                                               _work_bytes(work, work_bytes), _stream(stream)))
+
+
+def batch_parts_device(iov, nparts, max_part_bytes, out, work, work_bytes=None, seed=0, seeds=None, stream=None):
+    """copy_parts_device without the copy: out[i] = crc32c_extend(iov[i].base, n_i, seed_i), every part
+    cut over the chip. Async, capturable."""
+    _check(lib().photon_crc32c_batch_parts_n(_ptr(iov), nparts, max_part_bytes, seed & 0xFFFFFFFF, _ptr(seeds),
+                                             _ptr(out), _ptr(work), _work_bytes(work, work_bytes),
+                                             _stream(stream)))
+
+
+def batch_parts64_device(iov, nparts, max_part_bytes, out, work, work_bytes=None, seed=0, seeds=None, stream=None):
+    """batch_parts_device for CRC-64/ECMA (uint64 seeds / out)."""
+    _check(lib().photon_crc64ecma_batch_parts_n(_ptr(iov), nparts, max_part_bytes, seed & 0xFFFFFFFFFFFFFFFF,
+                                                _ptr(seeds), _ptr(out), _ptr(work), _work_bytes(work, work_bytes),
+                                                _stream(stream)))
 
 
 def series64_device(buffer, part_size, n_parts, out, stream=None):

@@ -508,6 +508,11 @@ struct Crc32c : Gf32 {
     static constexpr auto* kCombineKernel = &crc32c_combine_kernel;
     static constexpr auto* kTrimKernel = &crc32c_trim_kernel;
     static constexpr auto* kFoldPartsKernel = &crc32c_fold_parts_kernel;
+    typedef PartsArgs Parts;
+    template <int G, bool COPY>
+    static auto parts_kernel() { return &crc32c_parts_kernel<G, default_rows(G), COPY>; }
+    static constexpr auto* kPartsFoldKernel = &crc32c_parts_fold_kernel;
+    static constexpr const char* kPartsFoldLaunch = "crc32c_parts_fold_kernel launch";
     static constexpr auto* kCombineSeriesKernel = &crc32c_combine_series_kernel;
     // combine_series over empty parts: crc32c_combine_series_hw/sw return the
     // first nonzero part CRC (a kernel of its own). true = launched.
@@ -580,6 +585,15 @@ struct Crc64 : Gf64 {
     static constexpr auto* kCombineKernel = &crc64_combine_kernel;
     static constexpr auto* kTrimKernel = &crc64_trim_kernel;
     static constexpr auto* kFoldPartsKernel = &crc64_fold_parts_kernel;
+    typedef Parts64Args Parts;
+    // null: the copying form in an A/B build of the row loop (kCopying64)
+    template <int G, bool COPY>
+    static auto parts_kernel() {
+        if constexpr (COPY && !kCopying64) return static_cast<void (*)(Parts64Args, LaneConsts64)>(nullptr);
+        else return &crc64_parts_kernel<G, COPY>;
+    }
+    static constexpr auto* kPartsFoldKernel = &crc64_parts_fold_kernel;
+    static constexpr const char* kPartsFoldLaunch = "crc64_parts_fold_kernel launch";
     static constexpr auto* kCombineSeriesKernel = &crc64_combine_series_kernel;
     // No rule for empty parts: K = x^0 = 1 in crc64_combine_series_kernel.
     static bool combine_series_of_empty(const T*, uint32_t, uint32_t, T*, hipStream_t) { return false; }
@@ -1555,6 +1569,107 @@ int fold_parts_n(const typename W::T* d_crc, const uint64_t* d_len, const uint64
     return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, "_fold_parts_kernel launch");
 }
 
+// ------------------------------------------- many large parts
+// The piece of photon_crc{32c,64ecma}_{copy,batch}_parts_n: a multiple of 4
+// KiB, 0 = automatic (photon_crc_set_parts_piece).
+std::atomic<uint64_t> g_parts_piece{0};
+// 32 KiB: measured against 64 and 128 KiB (profiles/copy_parts_ab.jsonl)
+constexpr uint64_t kPartsPieceDefault = 32u << 10;
+
+uint64_t parts_piece_now() {
+    const uint64_t p = g_parts_piece.load(std::memory_order_relaxed);
+    return p ? p : kPartsPieceDefault;
+}
+
+// The plan of a call: the piece, the slots per part P and the task count;
+// false when nparts * P is beyond what the kernels index.
+struct PartsPlan {
+    uint64_t max_bytes, piece, per_part, ntasks;
+};
+bool parts_plan(uint64_t nparts, uint64_t max_part_bytes, uint64_t piece, PartsPlan* pl) {
+    pl->max_bytes = max_part_bytes < kPartsMaxBytes ? max_part_bytes : kPartsMaxBytes;
+    pl->piece = piece;
+    pl->per_part = parts_bound(pl->max_bytes, piece);
+    if (nparts > kPartsMaxTasks || pl->per_part > kPartsMaxTasks / (nparts ? nparts : 1)) return false;
+    pl->ntasks = nparts * pl->per_part;
+    return true;
+}
+
+// K^(2^i), K = x^(8 piece), for the part fold kernel: kept per thread while
+// the piece stays the same (it is a setting: every call of a process has it).
+template <typename W>
+const typename W::Pow& parts_pow_table(uint64_t piece) {
+    thread_local uint64_t made = 0;
+    thread_local typename W::Pow t;
+    if (made != piece) {
+        t = part_pow_table<W>(piece);
+        made = piece;
+    }
+    return t;
+}
+
+// The second launch of a parts call: a wavefront per part folds work[] into d_out.
+template <typename W>
+void launch_parts_fold(const photon_crc_iovec* d_src, uint64_t nparts, const PartsPlan& pl, const typename W::T* work,
+                       typename W::T seed0, const typename W::T* d_seeds, typename W::T* d_out, hipStream_t st) {
+    const uint64_t wpb = kPartsFoldBlock / 64, blocks = (nparts + wpb - 1) / wpb;
+    hipLaunchKernelGGL(W::kPartsFoldKernel, dim3(blocks < kPartsFoldMaxGrid ? blocks : kPartsFoldMaxGrid),
+                       dim3(kPartsFoldBlock), 0, st, d_src, nparts, pl.max_bytes, pl.piece, pl.per_part, work, seed0,
+                       d_seeds, d_out, parts_pow_table<W>(pl.piece), pow_table<W>());
+}
+
+// photon_crc32c_copy_parts_n / photon_crc32c_batch_parts_n and the CRC-64
+// forms: the piece kernel over nparts x P tasks on the batch kernels' grid
+// (lane groups by the piece size, W::copy_lanes; photon_crc_set_lanes_per_buffer
+// and photon_crc_set_batch_grid apply), then the part fold kernel, both on
+// `stream` inside one heavy-launch mark.
+template <typename W, bool COPY>
+int parts_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts, uint64_t max_part_bytes,
+            typename W::T seed0, const typename W::T* d_seeds, typename W::T* d_out, void* d_work,
+            uint64_t work_bytes, void* stream) {
+    typedef typename W::T T;
+    if (!nparts) return 0;
+    if (!d_src || !d_out || !d_work || (COPY && !d_dst))
+        return fail(-EINVAL, COPY ? "null descriptor array, destination array, output or workspace"
+                                  : "null descriptor array, output or workspace");
+    PartsPlan pl;
+    if (!parts_plan(nparts, max_part_bytes, parts_piece_now(), &pl))
+        return fail(-EINVAL, "too many tasks: " + std::to_string(nparts) + " parts of up to " +
+                                 std::to_string(max_part_bytes) + " bytes in pieces of " +
+                                 std::to_string(pl.piece) + " are more than " + std::to_string(kPartsMaxTasks));
+    const uint64_t need = pl.ntasks * sizeof(T);
+    if (work_bytes < need)
+        return fail(-EINVAL, "workspace too small: work_bytes " + std::to_string(work_bytes) + ", needed " +
+                                 std::to_string(need));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    typename W::Parts a{};
+    a.src = d_src;
+    a.dst = d_dst;
+    a.nparts = nparts;
+    a.max_bytes = pl.max_bytes;
+    a.piece = pl.piece;
+    a.per_part = pl.per_part;
+    a.ntasks = pl.ntasks;
+    a.work = static_cast<T*>(d_work);
+    int piece_rc = 0;
+    const int rc = launch_lanes<W>(pl.ntasks, W::copy_lanes(pl.piece), true, st, W::kPartsFoldLaunch,
+                                   [&](auto G, dim3 grid, const typename W::Lanes& kc) {
+        const auto kernel = W::template parts_kernel<decltype(G)::value, COPY>();
+        if (!kernel) {
+            piece_rc = fail(-ENOTSUP, "the copying CRC-64 kernels are not part of this A/B build");
+            return;
+        }
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, a, kc);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {  // no fold after a piece kernel that was not enqueued
+            piece_rc = hip_fail(e, W::kKernel, "_parts_kernel launch");
+            return;
+        }
+        launch_parts_fold<W>(d_src, nparts, pl, a.work, seed0, d_seeds, d_out, st);
+    });
+    return piece_rc ? piece_rc : rc;
+}
+
 }  // namespace
 
 // For the other translation units of the library (internal.h).
@@ -2270,6 +2385,91 @@ int photon_crc_test_fold_parts(int crc64, const void* crc, const uint64_t* len, 
         *result = fold_replay<Gf32>(static_cast<const uint32_t*>(crc), len, count, (uint32_t)seed, nthreads,
                                     pow_table<Crc32c>().x8pow2, total);
     return 0;
+}
+
+int photon_crc32c_copy_parts_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts,
+                               uint64_t max_part_bytes, uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_out,
+                               void* d_work, uint64_t work_bytes, void* stream) {
+    return parts_n<Crc32c, true>(d_src, d_dst, nparts, max_part_bytes, seed0, d_seeds, d_out, d_work, work_bytes,
+                                 stream);
+}
+
+int photon_crc64ecma_copy_parts_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts,
+                                  uint64_t max_part_bytes, uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out,
+                                  void* d_work, uint64_t work_bytes, void* stream) {
+    return parts_n<Crc64, true>(d_src, d_dst, nparts, max_part_bytes, seed0, d_seeds, d_out, d_work, work_bytes,
+                                stream);
+}
+
+int photon_crc32c_batch_parts_n(const photon_crc_iovec* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                                uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_out, void* d_work,
+                                uint64_t work_bytes, void* stream) {
+    return parts_n<Crc32c, false>(d_iov, nullptr, nparts, max_part_bytes, seed0, d_seeds, d_out, d_work, work_bytes,
+                                  stream);
+}
+
+int photon_crc64ecma_batch_parts_n(const photon_crc_iovec* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                                   uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out, void* d_work,
+                                   uint64_t work_bytes, void* stream) {
+    return parts_n<Crc64, false>(d_iov, nullptr, nparts, max_part_bytes, seed0, d_seeds, d_out, d_work, work_bytes,
+                                 stream);
+}
+
+uint64_t photon_crc_parts_work_bytes(uint64_t nparts, uint64_t max_part_bytes, int crc64) {
+    PartsPlan pl;
+    if (!parts_plan(nparts, max_part_bytes, parts_piece_now(), &pl)) return ~0ull;
+    return pl.ntasks * (crc64 ? sizeof(uint64_t) : sizeof(uint32_t));
+}
+
+int photon_crc_set_parts_piece(uint64_t bytes) {
+    if (bytes % kPartsAlign || bytes > kPartsMaxPiece)
+        return fail(-EINVAL, "parts piece: 0 (automatic) or a multiple of 4096 up to 1 GiB");
+    g_parts_piece.store(bytes, std::memory_order_relaxed);
+    return 0;
+}
+
+int photon_crc_util_parts_fold(int crc64, const void* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                               uint64_t seed0, const void* d_seeds, void* d_out, const void* d_work, void* stream) {
+    if (!nparts) return 0;
+    if (!d_iov || !d_out || !d_work) return fail(-EINVAL, "null argument");
+    const photon_crc_iovec* d_src = static_cast<const photon_crc_iovec*>(d_iov);
+    PartsPlan pl;
+    if (!parts_plan(nparts, max_part_bytes, parts_piece_now(), &pl)) return fail(-EINVAL, "too many tasks");
+    int cus = 0;
+    const int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (crc64)
+        launch_parts_fold<Crc64>(d_src, nparts, pl, static_cast<const uint64_t*>(d_work), seed0,
+                                 static_cast<const uint64_t*>(d_seeds), static_cast<uint64_t*>(d_out), st);
+    else
+        launch_parts_fold<Crc32c>(d_src, nparts, pl, static_cast<const uint32_t*>(d_work), (uint32_t)seed0,
+                                  static_cast<const uint32_t*>(d_seeds), static_cast<uint32_t*>(d_out), st);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, crc64 ? Crc64::kPartsFoldLaunch : Crc32c::kPartsFoldLaunch);
+}
+
+int photon_crc_test_parts_plan(uint64_t addr, uint64_t len, uint64_t max_part_bytes, uint64_t piece, uint64_t* out,
+                               int cap) {
+    if (!out || cap < 2 || piece % kPartsAlign || piece > kPartsMaxPiece) return fail(-EINVAL, "bad plan arguments");
+    PartsPlan pl;
+    if (!parts_plan(1, max_part_bytes, piece ? piece : parts_piece_now(), &pl)) return fail(-EINVAL, "too many tasks");
+    const uint64_t n = len < pl.max_bytes ? len : pl.max_bytes;
+    int k = 2;
+    uint64_t count = 0;
+    // every slot of the part, as the piece kernel walks them: the empty ones are left out
+    for (uint64_t j = 0; j < pl.per_part; ++j) {
+        const PartsPiece pc = parts_piece(addr, n, pl.piece, j);
+        if (!pc.len) continue;
+        if (k + 2 > cap) return fail(-EINVAL, "short output");
+        out[k++] = pc.off;
+        out[k++] = pc.len;
+        ++count;
+    }
+    if (count != parts_count(addr, n, pl.piece)) return fail(-EIO, "parts plan: piece count mismatch");
+    out[0] = pl.per_part;
+    out[1] = count;
+    return k;
 }
 
 int photon_crc32c_trim_batch(const photon_crc_component* d_all, const photon_crc_component* d_prefix,

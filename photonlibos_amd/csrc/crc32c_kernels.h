@@ -10,6 +10,7 @@
 #include "../../include/photon_crc/crc32c_gpu.h"
 #include "fold_parts.h"
 #include "gf2.h"
+#include "parts_plan.h"
 
 #ifndef PCRC_LANE_SEL
 #define PCRC_LANE_SEL 1  // per-lane v_perm selectors instead of rotating the word (+0.3 % on C2)
@@ -1700,6 +1701,112 @@ __global__ __launch_bounds__(kFoldMaxBlock) void crc32c_fold_parts_kernel(const 
                                                                           const uint32_t* seeds, uint32_t* out,
                                                                           uint64_t* total, PowTable pt) {
     fold_parts_block<Gf32>(crc, len, obj_start, nobj, nparts, seed0, seeds, out, total, pt.x8pow2);
+}
+
+// ------------------------------------------- many large parts, each cut over the chip
+// photon_crc32c_copy_parts_n / photon_crc32c_batch_parts_n:
+// nparts device-resident descriptors, each part cut into pieces by
+// parts_plan.h. The task space is nparts x per_part (the host's bound P on
+// the pieces of one part), part-major: task t is piece t % P of part t / P,
+// so neighbouring lane groups walk neighbouring pieces of one part, as the
+// batch kernel walks a strided batch. One lane group per task on the batch
+// kernels' persistent grid; the piece runs through the batch kernels' unit
+// from seed 0 (copy_begin + buffer_crc) and its CRC goes to work[t], a plain
+// store. A task behind the end of its part loads and stores nothing (a
+// wavefront whose tasks are all such skips the unit). The second launch
+// (crc32c_parts_fold_kernel) folds work[] into out[].
+template <typename T>
+struct PartsArgsT {
+    const photon_crc_iovec* src;
+    void* const* dst;          // COPY only
+    uint64_t nparts;
+    uint64_t max_bytes;        // the cap on every part's length
+    uint64_t piece;
+    uint64_t per_part;         // P
+    uint64_t ntasks;           // nparts * P
+    T* work;
+};
+typedef PartsArgsT<uint32_t> PartsArgs;
+
+// Task t of the space: the piece's source, length and (COPY) destination.
+template <bool COPY, typename A>
+__device__ __forceinline__ bool parts_task(const A& a, uint64_t t, const uint8_t** p, uint64_t* n, uint8_t** d) {
+    *p = nullptr;
+    *n = 0;
+    *d = nullptr;
+    if (t >= a.ntasks) return false;
+    const uint64_t i = t / a.per_part, j = t - i * a.per_part;
+    const photon_crc_iovec v = a.src[i];
+    const uint64_t len = v.len < a.max_bytes ? v.len : a.max_bytes;
+    const PartsPiece pc = parts_piece(reinterpret_cast<uint64_t>(v.base), len, a.piece, j);
+    if (!pc.len) return false;
+    *p = static_cast<const uint8_t*>(v.base) + pc.off;
+    *n = pc.len;
+    if constexpr (COPY) *d = static_cast<uint8_t*>(a.dst[i]) + pc.off;
+    return true;
+}
+
+template <int G, int U, bool COPY>
+__global__ __launch_bounds__(kBlock) void crc32c_parts_kernel(PartsArgs a, LaneConsts kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
+    constexpr bool kLead = PCRC_BATCH_LEAD || (U == 2 && PCRC_BATCH_LEAD2);  // as crc32c_batch_kernel
+    load_tables<G>(lds, kc);
+
+    constexpr int GPW = 64 / G;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    const LaneAddr la = lane_addr(lane);
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave_id(); wv * GPW < a.ntasks; wv += nwaves) {
+        const uint64_t t = wv * GPW + grp;
+        const uint8_t* p;
+        uint64_t n;
+        uint8_t* d;
+        const bool active = parts_task<COPY>(a, t, &p, &n, &d);
+        if (!__builtin_amdgcn_ballot_w64(active)) continue;  // wave-uniform
+        CopyTo ct;
+        if constexpr (COPY) {
+            if (active) ct = copy_begin<G>(p, d, n, gl);
+        }
+        const uint32_t crc = buffer_crc<G, U, kLead, COPY>(lds, p, n, 0u, gl, la, true, ct);
+        if (active && gl == 0) a.work[t] = crc;
+    }
+}
+
+// The part fold: one wavefront per part (parts beyond the grid: a stride
+// loop). The piece count and lengths are recomputed from src[i], so work[]
+// holds CRC words only, and only the words of real pieces are read.
+template <typename G>
+__device__ __forceinline__ void parts_fold_block(const photon_crc_iovec* src, uint64_t nparts, uint64_t max_bytes,
+                                                 uint64_t piece, uint64_t per_part, const typename G::T* work,
+                                                 typename G::T seed0, const typename G::T* seeds,
+                                                 typename G::T* out, const typename G::T* ktab,
+                                                 const typename G::T* tab) {
+    typedef typename G::T T;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wpb = blockDim.x >> 6;
+    for (uint64_t i = blockIdx.x * wpb + wave_id(); i < nparts; i += gridDim.x * wpb) {
+        const photon_crc_iovec v = src[i];
+        const uint64_t n = v.len < max_bytes ? v.len : max_bytes;
+        const T seed = seeds ? seeds[i] : seed0;
+        const T x = wave_xor(parts_fold_lane<G>(work + i * per_part, reinterpret_cast<uint64_t>(v.base), n, piece,
+                                                seed, lane, ktab, tab));
+        if (lane == 0) out[i] = x;
+    }
+}
+
+constexpr int kPartsFoldBlock = 256;  // 4 parts per workgroup
+constexpr uint64_t kPartsFoldMaxGrid = 1u << 20;
+
+// kp.x8pow2[i] = K^(2^i), K = x^(8 piece) (the host's constant); pt = x^(8 * 2^i).
+__global__ __launch_bounds__(kPartsFoldBlock) void crc32c_parts_fold_kernel(const photon_crc_iovec* src, uint64_t nparts,
+                                                                            uint64_t max_bytes, uint64_t piece,
+                                                                            uint64_t per_part, const uint32_t* work,
+                                                                            uint32_t seed0, const uint32_t* seeds,
+                                                                            uint32_t* out, PowTable kp, PowTable pt) {
+    parts_fold_block<Gf32>(src, nparts, max_bytes, piece, per_part, work, seed0, seeds, out, kp.x8pow2, pt.x8pow2);
 }
 
 // crc32c_trim (crc.cpp:442-464) per element, including its 32-bit size sum

@@ -453,7 +453,11 @@ __device__ __forceinline__ uint64_t finish_xor16(uint2 q, uint32_t d, const uint
 // CRC reads and under the condition that lets it into the CRC. The tiny
 // buffer's and the tail's bytes are walked by the group's first lane alone,
 // which stores each byte as it loads it.
-template <int G, bool COPY = false>
+// TAG: an instantiation of its own for a kernel added later (the parts
+// kernels take 1): the lambdas below are then not shared with the kernels
+// that were here before, whose inlining -- and so whose code -- would
+// otherwise change with the number of callers.
+template <int G, bool COPY = false, int TAG = 0>
 __device__ __forceinline__ uint64_t buffer_reg64(const uint32_t* lds, const uint8_t* p, uint64_t n, uint64_t init,
                                                  uint32_t gl, uint32_t lane, const LaneAddr64& la,
                                                  bool head = true, CopyTo ct = {}) {
@@ -1089,6 +1093,49 @@ __global__ __launch_bounds__(kFoldMaxBlock) void crc64_fold_parts_kernel(const u
                                                                          const uint64_t* seeds, uint64_t* out,
                                                                          uint64_t* total, PowTable64 pt) {
     fold_parts_block<Gf64>(crc, len, obj_start, nobj, nparts, seed0, seeds, out, total, pt.x8pow2);
+}
+
+// photon_crc64ecma_copy_parts_n / photon_crc64ecma_batch_parts_n (DESIGN.md
+// §4.9): crc32c_parts_kernel's task space and cut (parts_plan.h, parts_task)
+// with the CRC-64 unit. work[t] = crc64ecma_extend over the piece from seed 0
+// (the register from ~0, inverted: crc.cpp:119-122), which folds linearly.
+typedef PartsArgsT<uint64_t> Parts64Args;
+// The copying unit exists for the product's row loop only (buffer_reg64).
+constexpr bool kCopying64 = PCRC64_ABL == 0 && PCRC64_ROLL == 1 && PCRC64_U == 2;
+
+template <int G, bool COPY>
+__global__ __launch_bounds__(kBlock) void crc64_parts_kernel(Parts64Args a, LaneConsts64 kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
+    load_tables64<G>(lds, kc);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    constexpr int GPW = 64 / G;
+    const LaneAddr64 la = lane_addr64(lane);
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave_id(); wv * GPW < a.ntasks; wv += nwaves) {
+        const uint64_t t = wv * GPW + grp;
+        const uint8_t* p;
+        uint64_t n;
+        uint8_t* d;
+        const bool active = parts_task<COPY>(a, t, &p, &n, &d);
+        if (!__builtin_amdgcn_ballot_w64(active)) continue;  // wave-uniform
+        CopyTo ct;
+        if constexpr (COPY) {
+            if (active) ct = copy_begin<G>(p, d, n, gl);
+        }
+        const uint64_t reg = buffer_reg64<G, COPY, 1>(lds, p, n, ~0ull, gl, lane, la, true, ct);
+        if (active && gl == 0) a.work[t] = ~reg;
+    }
+}
+
+__global__ __launch_bounds__(kPartsFoldBlock) void crc64_parts_fold_kernel(const photon_crc_iovec* src, uint64_t nparts,
+                                                                           uint64_t max_bytes, uint64_t piece,
+                                                                           uint64_t per_part, const uint64_t* work,
+                                                                           uint64_t seed0, const uint64_t* seeds,
+                                                                           uint64_t* out, PowTable64 kp, PowTable64 pt) {
+    parts_fold_block<Gf64>(src, nparts, max_bytes, piece, per_part, work, seed0, seeds, out, kp.x8pow2, pt.x8pow2);
 }
 
 // The fold of crc64_copy_iov_seg_kernel's segment CRCs, one

@@ -75,6 +75,23 @@ the ratio (b)/(a), and the spread between the alternations of each arm;
                     the CPU replay of the kernel are compared before anything is timed.
                     "faster_3x" is true when host - device exceeds three times the spread
                     between host's alternations. --out appends.
+  --parts : copy + CRC of many large parts in one launch
+                    (photon_crc32c_copy_parts_n; with --crc64 the CRC-64 call), the same method,
+                    device to device, the parts back to back from buf+1 to dbuf+1 (co-aligned):
+                    1,024 x 4 MiB, 256 x 16 MiB, 64 x 64 MiB, 512 parts of seeded lengths of 1 to
+                    16 MiB, and 256 x 16 MiB to dbuf+10 (not co-aligned, no claim). "loop" = one
+                    copy_extend_device call per part on one stream (the route documented before);
+                    "parts" = the new call; "batch_iov" = copy_batch_iov over the same parts;
+                    "hand_built" (uniform shapes) = copy_batch_strided over 64 KiB pieces of the same
+                    bytes, then combine_series_device per part; "fold_only" = the new call's second
+                    launch alone (photon_crc_util_parts_fold); "parts_cap_1GiB" (ragged shape) = the
+                    new call with max_part_bytes = 1 GiB, whose difference to "parts" is the time of
+                    the empty tasks. Then "parts" at 32, 64 and 128 KiB pieces on the first two
+                    shapes, and the CRC-only calls (loop of extend_device, batch_parts, batch_iov; no
+                    claim). "faster_3x_than_X" is true when X - parts exceeds three times the spread
+                    between X's alternations; "not_slower_than_hand_built" when parts - hand_built is
+                    at most the larger of 3 % of hand_built and three times its spread. --shapes
+                    picks shapes by name; --out appends.
 """
 import argparse
 import csv
@@ -100,6 +117,7 @@ ap.add_argument("--iov-seg", action="store_true")
 ap.add_argument("--long", action="store_true")
 ap.add_argument("--sizes", default="64,256,1024", help="--long: payload sizes in MiB")
 ap.add_argument("--fold", action="store_true")
+ap.add_argument("--parts", action="store_true")
 ap.add_argument("--tree", default="working tree", help="--fold: a label of the tree measured, written to each line")
 args = ap.parse_args()
 
@@ -556,6 +574,187 @@ def bench_fold(crc64, nobj, per):
     res["faster_3x"] = bool(a - b > 3 * res["host"]["spread_us"])
     return res
 
+
+def alternate(arms):
+    """The §4.3 protocol over callables: --rounds alternations of --reps timed calls after --warmup each."""
+    means = {k: [] for k in arms}
+    times = {k: [] for k in arms}
+    for r in range(args.rounds):
+        for name in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+            fn = arms[name]
+            for _ in range(args.warmup):
+                fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.reps + 1)]
+            ev[0].record(st)
+            for k in range(args.reps):
+                fn()
+                ev[k + 1].record(st)
+            torch.cuda.synchronize()
+            t = [ev[k].elapsed_time(ev[k + 1]) for k in range(args.reps)]
+            times[name] += t
+            means[name].append(float(np.mean(t)))
+    res = {}
+    for name in arms:
+        ms = np.asarray(times[name])
+        res[name] = {"ms_mean": round(float(ms.mean()), 5), "ms_median": round(float(np.median(ms)), 5),
+                     "round_means_ms": [round(m, 5) for m in means[name]],
+                     "spread_ms": round(max(means[name]) - min(means[name]), 5)}
+    return res
+
+
+PARTS_SHAPES = {  # name: (parts, part MiB or None = seeded lengths of 1 to 16 MiB, destination delta)
+    "1024x4MiB": (1024, 4, 0), "256x16MiB": (256, 16, 0), "64x64MiB": (64, 64, 0), "512xragged": (512, None, 0),
+    "256x16MiB+9": (256, 16, 9),
+}
+
+
+def bench_parts(shape, what):
+    """what: "copy" = arms (a) loop of copy_extend_device, (b) copy_parts, (c) copy_batch_iov, (d) copy_batch_strided
+    over 64 KiB pieces + combine_series_device per part (uniform shapes), plus the part fold alone and, on the
+    ragged shape, (b) with max_part_bytes = 1 GiB (the empty tasks); "pieces" = (b) at 32, 64 and 128 KiB pieces;
+    "crc" = the CRC-only calls: loop of extend_device, batch_parts, batch_iov."""
+    nparts, mib, delta = PARTS_SHAPES[shape]
+    c64 = args.crc64
+    if mib is None:
+        lens = np.random.default_rng(0x9A27).integers(1 << 20, (16 << 20) + 1, nparts).astype(np.uint64)
+    else:
+        lens = np.full(nparts, mib << 20, np.uint64)
+    total, cap = int(lens.sum()), int(lens.max())
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+    src = torch.empty(total + 4096, dtype=torch.uint8, device="cuda")
+    dst = torch.zeros(total + 4096, dtype=torch.uint8, device="cuda")
+    assert src.data_ptr() % 4096 == 0 and dst.data_ptr() % 4096 == 0
+    ck.fill_splitmix(src, src.numel(), src.numel(), 1, 0x5EED0301)
+    s0, d0 = 1, 1 + delta
+    sp, dp = src.data_ptr() + s0, dst.data_ptr() + d0
+    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).cuda()
+    iov = np.empty((nparts, 2), np.uint64)
+    iov[:, 0] = np.uint64(sp) + offs
+    iov[:, 1] = lens
+    d_iov, d_dst = i64(iov), i64(np.uint64(dp) + offs)
+    dt, wdt = (torch.int64, np.uint64) if c64 else (torch.int32, np.uint32)
+    out = torch.zeros(nparts, dtype=dt, device="cuda")
+    pieces_k = (32, 64, 128)
+    ck.set_parts_piece(32 << 10)
+    work = torch.empty(max(ck.parts_work_bytes(nparts, 1 << 30 if mib is None else cap, c64), 8), dtype=torch.uint8,
+                       device="cuda")
+    ck.set_parts_piece(0)
+    wb = work.numel()
+    copy_parts = ck.copy_parts64_device if c64 else ck.copy_parts_device
+    batch_parts = ck.batch_parts64_device if c64 else ck.batch_parts_device
+    hl, ho = [int(x) for x in lens], [int(x) for x in offs]
+    op = [out.data_ptr() + k * out.element_size() for k in range(nparts)]
+
+    def loop():
+        for k in range(nparts):
+            if c64:
+                ck.copy_extend64_device(sp + ho[k], dp + ho[k], hl[k], op[k], stream=st)
+            else:
+                ck.copy_extend_device(sp + ho[k], dp + ho[k], hl[k], 0, op[k], stream=st)
+
+    def crc_loop():
+        for k in range(nparts):
+            if c64:
+                ck.extend64_device(sp + ho[k], hl[k], op[k], stream=st)
+            else:
+                ck.extend_device(sp + ho[k], hl[k], 0, op[k], stream=st)
+
+    def parts(max_bytes=cap):
+        copy_parts(d_iov, d_dst, nparts, max_bytes, out, work, wb, stream=st)
+
+    def sized(kib):
+        def f():
+            ck.set_parts_piece(kib << 10)
+            parts()
+        return f
+
+    def fold_only():
+        ck._check(lib().photon_crc_util_parts_fold(int(c64), d_iov.data_ptr(), nparts, cap, 0, None, out.data_ptr(),
+                                                   work.data_ptr(), st.cuda_stream))
+    piece = 65536
+    npiece = total // piece
+    pcrc = torch.zeros(max(npiece, 1), dtype=dt, device="cuda")
+    per = (mib << 20) // piece if mib else 0
+    pp = pcrc.data_ptr()
+
+    def hand_built():
+        if c64:
+            ck.copy_batch64_strided(sp, piece, dp, piece, piece, npiece, pcrc, stream=st)
+            for k in range(nparts):
+                ck.combine_series64_device(pp + k * per * out.element_size(), piece, per, op[k], stream=st)
+        else:
+            ck.copy_batch_strided(sp, piece, dp, piece, piece, npiece, pcrc, stream=st)
+            for k in range(nparts):
+                ck.combine_series_device(pp + k * per * out.element_size(), piece, per, op[k], stream=st)
+    if what == "copy":
+        arms = {"loop": loop, "parts": parts,
+                "batch_iov": lambda: (ck.copy_batch64_iov if c64 else ck.copy_batch_iov)(d_iov, d_dst, nparts, out,
+                                                                                         stream=st)}
+        if mib is not None and delta % 16 == 0:
+            arms["hand_built"] = hand_built
+        if mib is None:
+            arms["parts_cap_1GiB"] = lambda: parts(1 << 30)
+    elif what == "pieces":
+        arms = {f"parts_{k}KiB": sized(k) for k in pieces_k}
+    else:
+        arms = {"loop": crc_loop, "parts": lambda: batch_parts(d_iov, nparts, cap, out, work, wb, stream=st),
+                "batch_iov": lambda: (ck.batch64_iov if c64 else ck.batch_iov)(d_iov, nparts, out, stream=st)}
+    crcs = {}
+    for name, fn in arms.items():  # same CRCs, the right bytes landed, before anything is timed
+        dst.zero_()
+        out.fill_(-1)
+        work.fill_(0x5A)
+        fn()
+        torch.cuda.synchronize()
+        if what != "crc":
+            assert torch.equal(dst[d0:d0 + total], src[s0:s0 + total]), f"{name}: destination differs from the source"
+            assert not bool(dst[:d0].any()) and not bool(dst[d0 + total:].any()), f"{name}: wrote outside"
+        crcs[name] = out.cpu().numpy().view(wdt).copy()
+    first = next(iter(crcs))
+    for name in crcs:
+        assert np.array_equal(crcs[first], crcs[name]), f"the CRCs of {first} and {name} differ"
+    if what == "copy":
+        arms["fold_only"] = fold_only  # the second launch of "parts" alone, over the workspace it left
+        parts()
+        fold_only()
+        torch.cuda.synchronize()
+        assert np.array_equal(out.cpu().numpy().view(wdt), crcs[first]), "fold_only differs"
+    res = {"shape": "parts", "what": what, "crc": "crc64ecma" if c64 else "crc32c", "layout": shape, "nparts": nparts,
+           "bytes": total, "src": "buf+1", "dst": f"dbuf+{d0}", "co_aligned": delta % 16 == 0,
+           "rounds": args.rounds, "reps": args.reps, "warmup": args.warmup}
+    res.update(alternate(arms))
+    ck.set_parts_piece(0)
+    gib = total / 2.0**30
+    for name in arms:
+        if name != "fold_only":
+            res[name]["payload_GiBps_mean"] = round(gib / (res[name]["ms_mean"] * 1e-3), 1)
+    if what != "pieces":
+        b = res["parts"]["ms_mean"]
+        for other in ("loop", "batch_iov"):
+            o = res[other]
+            res[f"margin_over_{other}_spread"] = round((o["ms_mean"] - b) / max(o["spread_ms"], 1e-9), 2)
+            res[f"faster_3x_than_{other}"] = bool(o["ms_mean"] - b > 3 * o["spread_ms"])
+        if "hand_built" in res:
+            d = res["hand_built"]
+            res["allowed_over_hand_built_ms"] = round(max(0.03 * d["ms_mean"], 3 * d["spread_ms"]), 5)
+            res["not_slower_than_hand_built"] = bool(b - d["ms_mean"] <= res["allowed_over_hand_built_ms"])
+        if "parts_cap_1GiB" in res:
+            res["empty_tasks_ms"] = round(res["parts_cap_1GiB"]["ms_mean"] - b, 5)
+    return res
+
+
+if args.parts:
+    plan = [(s, "copy") for s in PARTS_SHAPES] + [("1024x4MiB", "pieces"), ("256x16MiB", "pieces"),
+                                                  ("256x16MiB", "crc")]
+    for shape, what in plan:
+        if args.shapes != "c2,c3" and shape not in args.shapes.split(","):
+            continue
+        line = json.dumps(bench_parts(shape, what))
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+    sys.exit(0)
 
 if args.fold:
     for c64 in (False, True):
