@@ -9,6 +9,7 @@ import pytest
 
 from photonlibos_amd import checksum as ck
 from photonlibos_amd import datagen
+from tests.test_gpu_batch_rounds import units
 
 pytestmark = pytest.mark.gpu
 
@@ -136,18 +137,22 @@ def test_message_segment_crcs_many_rounds(dev_pool, oracle, lanes):
     # Segment CRCs of the one-kernel message form, which holds a lane's
     # segment-CRC stores back (two per lane) until a third arrives or the wave
     # ends: messages of up to 40 segments (several store events per lane and
-    # message) and enough messages that every wave runs several rounds.
+    # message) and enough messages that every wave runs several rounds. This
+    # launcher's grid is one workgroup per CU whatever set_batch_grid says, so
+    # the rounds come from the count: at least units() messages (three rounds;
+    # tests/test_gpu_batch_rounds.py), 8 lanes being what automatic lanes take.
     torch, host, d = dev_pool
     rnd = random.Random(7000 + lanes)
     ck.set_msg_mode(1)
     ck.set_lanes_per_buffer(lanes)
     iov, start, msgs = [], [0], []
-    nmsg = 120000 if lanes in (0, 4, 8) else 3000
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    nmsg = max(120000 if lanes in (0, 4, 8) else 0, units(cus, lanes or 8, False))
     for m in range(nmsg):
         k = rnd.choice([1, 2, 3]) if m % 50 else rnd.randrange(17, 41)
         parts = []
         for _ in range(k):
-            n = rnd.randrange(0, 600) if lanes in (0, 4, 8) else rnd.randrange(0, 20000)
+            n = rnd.randrange(0, 600) if lanes in (0, 4, 8) else rnd.randrange(0, 4000)
             o = rnd.randrange(0, POOL - n)
             iov.append((d.data_ptr() + o, n))
             parts.append((o, n))
