@@ -160,6 +160,21 @@ int photon_crc_test_tables(int which, uint32_t* out, int n);
 int photon_crc_test_long_plan(uint64_t addr, uint64_t n, int cus, int lanes, int rounds, int crc64, uint64_t* out,
                               int nout);
 
+/* The one-buffer layout (crc32c_kernels.h "one small buffer") the launch
+ * paths of photon_crc32c_extend_device / photon_crc64ecma_extend_device and
+ * of the routed crc32c_extend / crc64ecma_extend would take for a buffer at
+ * address `addr` (not dereferenced) of n bytes, by the same geometry code
+ * they call, under the current photon_crc_set_mid_kernel setting:
+ * out[0] = layout (0 small, 1 mid, 2 the long kernel), out[1..7] = nb, s0,
+ * eoff, k, rows, grid (workgroups launched), wg0 (all 0 for layout 2),
+ * out[8] = 1 if the block span fits the resident service, then the layout
+ * constants: out[9..18] = small V, small workgroups, mid V, mid workgroups,
+ * the small block limit, the mid block limit, small rows, mid rows, the
+ * service's block limit, the seed bytes of the width (4 or 8). For CPU tests
+ * that pin a table of shapes to the geometry. Returns the words written
+ * (19), or -EINVAL (null or short output). */
+int photon_crc_test_small_plan(uint64_t addr, uint64_t n, int crc64, uint64_t* out, int nout);
+
 /* Piece size of photon_crc32c_copy_parts_n / photon_crc32c_batch_parts_n and
  * the CRC-64 forms (testing / tuning): 0 = automatic (32 KiB, DESIGN.md
  * §4.9), else a multiple of 4 KiB from 4 KiB to 1 GiB. It sets the slots per

@@ -734,9 +734,25 @@ def set_routed_wait(spin_us=40, sleep_ahead=True):
 
 
 def set_mid_kernel(on=True):
-    """Spans over 256 KiB up to 32 MiB: the mid layout (default) or, off, the
+    """Spans over 256 KiB up to 16 MiB: the mid layout (default) or, off, the
     long kernel (tuning; tests of the long kernel's plan)."""
     _check(lib().photon_crc_set_mid_kernel(1 if on else 0))
+
+
+SMALL_PLAN_FIELDS = ("layout", "nb", "s0", "eoff", "k", "rows", "grid", "wg0", "fits_service",
+                     "small_v", "small_wg", "mid_v", "mid_wg", "small_blocks", "mid_blocks",
+                     "small_rows", "mid_rows", "svc_max_blocks", "seed_bytes")
+
+
+def small_plan(addr, nbytes, crc64=False):
+    """photon_crc_test_small_plan (tuning.h) as a dict of SMALL_PLAN_FIELDS: the one-buffer
+    layout (0 small, 1 mid, 2 the long kernel) and geometry the launch paths would take for
+    nbytes at address addr (not dereferenced), and the layout constants (tests)."""
+    out = (ctypes.c_uint64 * len(SMALL_PLAN_FIELDS))()
+    k = lib().photon_crc_test_small_plan(addr, nbytes, 1 if crc64 else 0, out, len(out))
+    _check(k if k < 0 else 0)
+    assert k == len(SMALL_PLAN_FIELDS), k
+    return dict(zip(SMALL_PLAN_FIELDS, (int(x) for x in out)))
 
 
 def set_small_service(idle_us):

@@ -1285,6 +1285,34 @@ bool mid_args(const void* p, uint64_t n, typename W::T seed, typename W::Small* 
     return true;
 }
 
+// photon_crc_test_small_plan for one CRC width: the launch paths' own
+// small_args / mid_args (extend_device, dispatch_crc), nothing launched.
+template <typename W>
+int test_small_plan(const void* p, uint64_t n, uint64_t* out, int nout) {
+    typename W::Small sa{};
+    uint32_t grid = 0, v = 0, layout = 2;
+    const bool svc = small_args<W>(p, n, 0, &sa, &grid, kSvcMaxBlocks);  // as dispatch_crc asks
+    sa = typename W::Small{};
+    if (small_args<W>(p, n, 0, &sa, &grid)) {
+        layout = 0;
+        v = kSmallLanes;
+    } else if (mid_args<W>(p, n, 0, &sa, &grid)) {
+        layout = 1;
+        v = kMidLanes;
+    } else {  // the long kernel's case: no block grid
+        sa = typename W::Small{};
+        grid = 0;
+    }
+    const uint64_t rows = v ? (sa.nb + v - 1) / v : 0;  // as small_wave_value / small_load count them
+    const uint64_t w[] = {layout, sa.nb, sa.s0, sa.eoff, sa.k, rows, grid, sa.wg0, svc,
+                          kSmallLanes, kSmallWg, kMidLanes, kMidWg, kSmallBlocks, W::kMidBlocks,
+                          kSmallRows, W::kMidRows, kSvcMaxBlocks, W::kSeedBytes};
+    constexpr int kn = (int)(sizeof w / sizeof w[0]);
+    if (nout < kn) return fail(-EINVAL, "short output");
+    memcpy(out, w, sizeof w);
+    return kn;
+}
+
 // The long kernel for photon_crc32c_extend_device / photon_crc64ecma_extend_device
 // (and, with a tag, for a routed call whose result lands tagged in pinned memory).
 template <typename W>
@@ -1771,6 +1799,12 @@ int photon_crc_test_long_plan(uint64_t addr, uint64_t n, int cus, int lanes, int
     if ((int)w.size() > nout) return fail(-EINVAL, "short output");
     memcpy(out, w.data(), w.size() * 8);
     return (int)w.size();
+}
+
+int photon_crc_test_small_plan(uint64_t addr, uint64_t n, int crc64, uint64_t* out, int nout) {
+    if (!out) return fail(-EINVAL, "null output");
+    const void* p = reinterpret_cast<const void*>(addr);
+    return crc64 ? test_small_plan<Crc64>(p, n, out, nout) : test_small_plan<Crc32c>(p, n, out, nout);
 }
 
 int photon_crc_set_generic_rows(int rows_per_step) {

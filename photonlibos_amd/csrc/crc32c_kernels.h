@@ -2426,7 +2426,7 @@ struct SmallArgs {
     uint32_t* acc;       // long_reduce state (grid > 1, slots == nullptr)
     uint64_t tbase;      // long_reduce ticket base
     uint32_t treset;
-    uint32_t nb;         // blocks of the grid, <= kSmallBlocks + 1
+    uint32_t nb;         // blocks of the grid: <= kSmallBlocks (small), kMidBlocks (mid), kSvcMaxBlocks (service)
     uint32_t s0;         // data start - a0 (0..15)
     uint32_t eoff;       // data end - a0: bytes at or past it are zero
     uint32_t k;          // grid end - data end (0..31): the result is multiplied by x^(-8k)

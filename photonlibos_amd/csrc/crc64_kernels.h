@@ -1440,7 +1440,7 @@ struct Small64Args {
     uint64_t* acc;           // long_reduce state
     uint64_t tbase;
     uint32_t treset;
-    uint32_t nb;             // blocks of the grid, <= kSmallBlocks + 1
+    uint32_t nb;             // blocks of the grid: <= kSmallBlocks, kMid64Blocks (mid), kSvcMaxBlocks (service)
     uint32_t s0;             // data start - a0
     uint32_t eoff;           // data end - a0
     uint32_t k;              // grid end - data end: the register is multiplied by x^(-8k)
