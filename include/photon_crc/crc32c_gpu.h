@@ -578,6 +578,84 @@ int photon_crc64ecma_fold_parts_n(const uint64_t* d_crc, const uint64_t* d_len,
                                   uint64_t seed0, const uint64_t* d_seeds,
                                   uint64_t* d_out, uint64_t* d_total, void* stream);
 
+/* Check stored CRCs on the device: the step after any call above that left
+ * `count` computed words in d_crc, on the same stream, with nothing in
+ * between. Entry i is BAD when d_crc[i] differs from its expected word.
+ *   verify_n: the expected word of entry i is the little-endian word at
+ *     (const char*)d_expected + i * expected_stride, at ANY address (it is
+ *     read by a word load where aligned and bytewise elsewhere, never by a
+ *     misaligned word load) and with any stride >= the word width (4, or 8
+ *     for CRC-64). Stride = width is a dense array; stride 8 / 16 with the CRC
+ *     first is a CRC32C_Component / CRC64ECMA_Component array; d_expected =
+ *     base + nbytes with expected_stride = stride is the trailer behind each
+ *     payload of a strided batch (net/test/zerocopy-client.cpp:112-118). A
+ *     stride below the width with count > 1 gives -EINVAL.
+ *   verify_ptr_n: d_expected_ptr[i] points at entry i's expected word, any
+ *     alignment (e.g. iov[i].base + iov[i].len, built by the caller like the
+ *     d_dst[] lists). A null pointer means entry i is NOT COMPARED: neither
+ *     bad nor counted in the report's count (blocks with no stored CRC).
+ * Result: all four words of *d_report are written by every call with count >
+ * 0; d_bad_idx[0 .. nlisted) holds the bad indices in ASCENDING order, and
+ * nothing at or beyond d_bad_idx[nlisted] is written. d_bad_idx may be null
+ * when bad_cap == 0 (count only). d_report and d_bad_idx may be pinned host
+ * memory: the host reads them after the stream's sync with no copy.
+ *   - count == 0 returns 0 and touches NOTHING, the report included.
+ *   - A null d_crc, d_expected / d_expected_ptr, d_report or d_work, or a null
+ *     d_bad_idx with bad_cap > 0, gives -EINVAL ("null ..." in
+ *     photon_crc_last_error()).
+ *   - d_work: device memory of at least photon_crc_verify_work_bytes(count)
+ *     bytes (work_bytes says how many it has), 8-byte aligned; it needs no
+ *     clearing and keeps nothing between calls. A work_bytes too small gives
+ *     -EINVAL (both numbers in the error text), and so does a count for which
+ *     photon_crc_verify_work_bytes returns ~0 (more than 2^40 entries).
+ * Asynchronous on `stream`. The calls allocate nothing and synchronise
+ * nothing and write with plain stores only: no atomics, no memset, no
+ * per-stream state -- the result is deterministic, a call is capturable into
+ * a graph and replayable any number of times, and calls may run concurrently
+ * with distinct d_report / d_bad_idx / d_work. No CPU fallback. At most three
+ * launches (mark the tiles, scan their counts and write the report, list the
+ * indices; the last one only with bad_cap > 0). */
+typedef struct photon_crc_verify_report {
+    uint64_t nbad;      /* compared entries whose computed word != expected word */
+    uint64_t first_bad; /* the lowest such index, ~0ull when nbad == 0 */
+    uint64_t nlisted;   /* min(nbad, bad_cap): entries written to d_bad_idx */
+    uint64_t count;     /* entries compared (count minus the entries with a null pointer) */
+} photon_crc_verify_report;
+
+uint64_t photon_crc_verify_work_bytes(uint64_t count);
+
+int photon_crc32c_verify_n(const uint32_t* d_crc, const void* d_expected, uint64_t expected_stride,
+                           uint64_t count, photon_crc_verify_report* d_report,
+                           uint64_t* d_bad_idx, uint64_t bad_cap,
+                           void* d_work, uint64_t work_bytes, void* stream);
+int photon_crc32c_verify_ptr_n(const uint32_t* d_crc, const void* const* d_expected_ptr,
+                               uint64_t count, photon_crc_verify_report* d_report,
+                               uint64_t* d_bad_idx, uint64_t bad_cap,
+                               void* d_work, uint64_t work_bytes, void* stream);
+int photon_crc64ecma_verify_n(const uint64_t* d_crc, const void* d_expected, uint64_t expected_stride,
+                              uint64_t count, photon_crc_verify_report* d_report,
+                              uint64_t* d_bad_idx, uint64_t bad_cap,
+                              void* d_work, uint64_t work_bytes, void* stream);
+int photon_crc64ecma_verify_ptr_n(const uint64_t* d_crc, const void* const* d_expected_ptr,
+                                  uint64_t count, photon_crc_verify_report* d_report,
+                                  uint64_t* d_bad_idx, uint64_t bad_cap,
+                                  void* d_work, uint64_t work_bytes, void* stream);
+
+/* The mirror of the verify calls, for the write side: word i of d_crc is
+ * written little-endian to (char*)d_dst + i * dst_stride (stamp_n) or to
+ * d_dst_ptr[i] (stamp_ptr_n; a null pointer skips the entry), at any
+ * alignment -- e.g. the dense d_out[] of photon_crc32c_copy_batch_strided
+ * placed behind each landed payload. Exactly 4 (CRC-64: 8) bytes are written
+ * per entry, as one word where aligned and bytewise elsewhere; nothing is
+ * read-modify-written. A dst_stride below the width with count > 1 gives
+ * -EINVAL; a null d_crc or d_dst / d_dst_ptr gives -EINVAL ("null ..."); count
+ * == 0 returns 0 and touches nothing. Asynchronous on `stream`, one launch,
+ * no workspace; allocation, capture and concurrency as the verify calls. */
+int photon_crc32c_stamp_n(const uint32_t* d_crc, uint64_t count, void* d_dst, uint64_t dst_stride, void* stream);
+int photon_crc32c_stamp_ptr_n(const uint32_t* d_crc, uint64_t count, void* const* d_dst_ptr, void* stream);
+int photon_crc64ecma_stamp_n(const uint64_t* d_crc, uint64_t count, void* d_dst, uint64_t dst_stride, void* stream);
+int photon_crc64ecma_stamp_ptr_n(const uint64_t* d_crc, uint64_t count, void* const* d_dst_ptr, void* stream);
+
 /* Synchronous convenience: photon_crc32c_batch_strided + stream sync. */
 int photon_crc32c_batch_strided_sync(const void* d_base, uint64_t stride, uint64_t nbytes, uint64_t count,
                                      uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_out, void* stream);

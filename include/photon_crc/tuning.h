@@ -220,6 +220,34 @@ int photon_crc_test_fold_parts(int crc64, const void* crc, const uint64_t* len, 
 int photon_crc_util_fold_on_host(int crc64, const void* d_crc, const uint64_t* h_len, const uint64_t* h_obj_start,
                                  uint64_t nobj, uint64_t nparts, uint64_t seed, void* h_out, void* stream);
 
+/* Tile of photon_crc32c_verify_n / _verify_ptr_n and the CRC-64 forms in
+ * entries (testing / tuning): 0 = the default (1,024), else
+ * a power of two from 64 to 65,536. It sets the tile count and so
+ * photon_crc_verify_work_bytes: size the workspace after setting it. */
+int photon_crc_set_verify_tile(uint32_t entries);
+
+/* CPU replay of the verify kernels (photon_crc32c_verify_n / _verify_ptr_n
+ * and the CRC-64 forms; photonlibos_amd/csrc/verify_scan.h): the mark, scan
+ * and list steps run on host arrays for tiles of `tile` entries. crc[] is
+ * uint64_t words if crc64, else uint32_t; expected words by expected_stride
+ * from `expected`, or, when expected_ptr is not null, by pointer (null
+ * entries are not compared). report[] = the four words of
+ * photon_crc_verify_report, bad_idx[0 .. report[2]) the listed indices.
+ * Returns 0, or -EINVAL (a null argument, count == 0, a bad tile). */
+int photon_crc_test_verify(int crc64, const void* crc, const void* expected, uint64_t expected_stride,
+                           const void* const* expected_ptr, uint64_t count, uint32_t tile, uint64_t bad_cap,
+                           uint64_t report[4], uint64_t* bad_idx);
+
+/* Bench utility (scripts/bench_copy_crc.py --verify, arm (a)): the route a
+ * caller took before the verify calls existed, natively:
+ * photon_crc_stream_sync(stream), the `count` CRC words at d_crc copied into
+ * the caller's host buffer h_crc (pinned, for the fastest copy), then a
+ * compare loop against the dense host array h_expected (uint32_t or, if
+ * crc64, uint64_t words): report[] and h_bad_idx as the verify calls give
+ * them. Synchronous. */
+int photon_crc_util_verify_on_host(int crc64, const void* d_crc, void* h_crc, const void* h_expected, uint64_t count,
+                                   uint64_t report[4], uint64_t* h_bad_idx, uint64_t bad_cap, void* stream);
+
 /* Test/bench utility (not on the checksum path): fill count buffers of
  * nbytes at d_base + i*stride with the splitmix64 byte stream of seed
  * (seed_base + i), i.e. word k = mix64(seed + (k+1)*0x9E3779B97F4A7C15),

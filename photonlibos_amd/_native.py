@@ -129,6 +129,18 @@ def _declare(L):
     fn("photon_crc_set_parts_piece", ctypes.c_int, u64)
     fn("photon_crc_util_parts_fold", ctypes.c_int, ctypes.c_int, vp, u64, u64, u64, vp, vp, vp, vp)
     fn("photon_crc_test_parts_plan", ctypes.c_int, u64, u64, u64, u64, vp, ctypes.c_int)
+    fn("photon_crc_verify_work_bytes", u64, u64)
+    fn("photon_crc32c_verify_n", ctypes.c_int, vp, vp, u64, u64, vp, vp, u64, vp, u64, vp)
+    fn("photon_crc64ecma_verify_n", ctypes.c_int, vp, vp, u64, u64, vp, vp, u64, vp, u64, vp)
+    fn("photon_crc32c_verify_ptr_n", ctypes.c_int, vp, vp, u64, vp, vp, u64, vp, u64, vp)
+    fn("photon_crc64ecma_verify_ptr_n", ctypes.c_int, vp, vp, u64, vp, vp, u64, vp, u64, vp)
+    fn("photon_crc32c_stamp_n", ctypes.c_int, vp, u64, vp, u64, vp)
+    fn("photon_crc64ecma_stamp_n", ctypes.c_int, vp, u64, vp, u64, vp)
+    fn("photon_crc32c_stamp_ptr_n", ctypes.c_int, vp, u64, vp, vp)
+    fn("photon_crc64ecma_stamp_ptr_n", ctypes.c_int, vp, u64, vp, vp)
+    fn("photon_crc_set_verify_tile", ctypes.c_int, u32)
+    fn("photon_crc_test_verify", ctypes.c_int, ctypes.c_int, vp, vp, u64, vp, u64, u32, u64, vp, vp)
+    fn("photon_crc_util_verify_on_host", ctypes.c_int, ctypes.c_int, vp, vp, vp, u64, vp, vp, u64, vp)
     # include/photon_crc/checked_batch.h
     fn("photon_crc_pinned_allocate", ctypes.c_int, vp, PhotonRange, ctypes.POINTER(vp))
     fn("photon_crc_pinned_deallocate", ctypes.c_int, vp, vp)

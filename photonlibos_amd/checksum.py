@@ -37,6 +37,9 @@ __all__ = [
     "set_parts_piece",
     "series64_device", "combine_series64_device", "fold_parts_device", "fold_parts64_device",
     "crc64ecma_series_at", "crc64ecma_combine_series_at",
+    "VerifyReport", "verify_work_bytes", "set_verify_tile",
+    "verify_device", "verify64_device", "verify_ptr_device", "verify64_ptr_device",
+    "stamp_device", "stamp64_device", "stamp_ptr_device", "stamp64_ptr_device",
     "batch64_strided", "batch64_iov", "combine64_batch", "trim64_batch", "batch64_msg_n", "host_batch64_strided", "extend64_device", "extend_spans", "extend64_spans", "Span", "combine_batch", "fill_splitmix", "read_stream", "IOVEC_DTYPE",
 ]
 
@@ -595,6 +598,78 @@ def fold_parts64_device(crcs, lens, obj_start, nobj, nparts, out, seed=0, seeds=
     _check(lib().photon_crc64ecma_fold_parts_n(_ptr(crcs), _ptr(lens), _ptr(obj_start), nobj, nparts,
                                                seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(out), _ptr(total),
                                                _stream(stream)))
+
+
+class VerifyReport(ctypes.Structure):
+    """photon_crc_verify_report (include/photon_crc/crc32c_gpu.h)."""
+    _fields_ = [("nbad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64), ("nlisted", ctypes.c_uint64),
+                ("count", ctypes.c_uint64)]
+
+
+def verify_work_bytes(count):
+    """Bytes of workspace verify*_device needs for `count` entries under the current tile (set_verify_tile)."""
+    return lib().photon_crc_verify_work_bytes(count)
+
+
+def set_verify_tile(entries):
+    """Tile of the verify calls: 0 = the default (1,024), else a power of two from 64 to 65,536 (tuning.h)."""
+    _check(lib().photon_crc_set_verify_tile(entries))
+
+
+def verify_device(crcs, expected, expected_stride, count, report, bad_idx, bad_cap, work, work_bytes=None,
+                  stream=None):
+    """Check `count` computed CRC-32C words (uint32, device) against stored ones on the device: entry i is
+    bad when crcs[i] differs from the little-endian word at expected + i*expected_stride (any address, any
+    stride >= 4). report: a VerifyReport's four uint64 words (device or pinned host memory): nbad, first_bad
+    (~0 if none), nlisted, count; bad_idx[0:nlisted] (uint64) = the bad indices in ascending order, nlisted =
+    min(nbad, bad_cap); bad_idx may be None with bad_cap 0. work: device workspace of at least
+    verify_work_bytes(count) bytes (work_bytes, or the tensor's size). Async, capturable."""
+    _check(lib().photon_crc32c_verify_n(_ptr(crcs), _ptr(expected), expected_stride, count, _ptr(report),
+                                        _ptr(bad_idx), bad_cap, _ptr(work), _work_bytes(work, work_bytes),
+                                        _stream(stream)))
+
+
+def verify64_device(crcs, expected, expected_stride, count, report, bad_idx, bad_cap, work, work_bytes=None,
+                    stream=None):
+    """verify_device for CRC-64/ECMA (uint64 words, any stride >= 8)."""
+    _check(lib().photon_crc64ecma_verify_n(_ptr(crcs), _ptr(expected), expected_stride, count, _ptr(report),
+                                           _ptr(bad_idx), bad_cap, _ptr(work), _work_bytes(work, work_bytes),
+                                           _stream(stream)))
+
+
+def verify_ptr_device(crcs, expected_ptrs, count, report, bad_idx, bad_cap, work, work_bytes=None, stream=None):
+    """verify_device with entry i's expected word at expected_ptrs[i] (a device array of pointers, any
+    alignment); a null pointer means the entry is not compared: neither bad nor in report.count."""
+    _check(lib().photon_crc32c_verify_ptr_n(_ptr(crcs), _ptr(expected_ptrs), count, _ptr(report), _ptr(bad_idx),
+                                            bad_cap, _ptr(work), _work_bytes(work, work_bytes), _stream(stream)))
+
+
+def verify64_ptr_device(crcs, expected_ptrs, count, report, bad_idx, bad_cap, work, work_bytes=None, stream=None):
+    """verify_ptr_device for CRC-64/ECMA (uint64 words)."""
+    _check(lib().photon_crc64ecma_verify_ptr_n(_ptr(crcs), _ptr(expected_ptrs), count, _ptr(report),
+                                               _ptr(bad_idx), bad_cap, _ptr(work), _work_bytes(work, work_bytes),
+                                               _stream(stream)))
+
+
+def stamp_device(crcs, count, dst, dst_stride, stream=None):
+    """Write CRC-32C word i little-endian at dst + i*dst_stride, any alignment, exactly 4 bytes each (the
+    trailer behind each payload of a strided batch). Async, capturable."""
+    _check(lib().photon_crc32c_stamp_n(_ptr(crcs), count, _ptr(dst), dst_stride, _stream(stream)))
+
+
+def stamp64_device(crcs, count, dst, dst_stride, stream=None):
+    """stamp_device for CRC-64/ECMA (uint64 words, 8 bytes each)."""
+    _check(lib().photon_crc64ecma_stamp_n(_ptr(crcs), count, _ptr(dst), dst_stride, _stream(stream)))
+
+
+def stamp_ptr_device(crcs, count, dst_ptrs, stream=None):
+    """stamp_device with word i written at dst_ptrs[i] (a device array of pointers; null skips the entry)."""
+    _check(lib().photon_crc32c_stamp_ptr_n(_ptr(crcs), count, _ptr(dst_ptrs), _stream(stream)))
+
+
+def stamp64_ptr_device(crcs, count, dst_ptrs, stream=None):
+    """stamp_ptr_device for CRC-64/ECMA (uint64 words)."""
+    _check(lib().photon_crc64ecma_stamp_ptr_n(_ptr(crcs), count, _ptr(dst_ptrs), _stream(stream)))
 
 
 class Span(ctypes.Structure):

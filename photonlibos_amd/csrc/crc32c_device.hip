@@ -1597,6 +1597,89 @@ int fold_parts_n(const typename W::T* d_crc, const uint64_t* d_len, const uint64
     return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, "_fold_parts_kernel launch");
 }
 
+// ------------------------------------- stored CRCs checked on the device
+// The tile of the verify calls in entries: a power of two, 0 = the default
+// (photon_crc_set_verify_tile).
+std::atomic<uint32_t> g_verify_tile{0};
+// 1,024: measured against 256, 4,096, 16,384 and 65,536 (profiles/verify_ab.jsonl)
+constexpr uint32_t kVerifyTileDefault = 1024;
+
+uint32_t verify_tile_now() {
+    const uint32_t t = g_verify_tile.load(std::memory_order_relaxed);
+    return t ? t : kVerifyTileDefault;
+}
+
+uint32_t verify_grid(uint64_t units) { return units < kVerifyMaxGrid ? (uint32_t)units : kVerifyMaxGrid; }
+
+// photon_crc32c_verify_n / _verify_ptr_n and the CRC-64 forms: expected words
+// by stride (d_expected) or by pointer (d_expected_ptr), the other one null.
+// mark, scan and, with bad_cap > 0, list, on `stream`.
+template <typename W>
+int verify_n(const typename W::T* d_crc, const void* d_expected, uint64_t expected_stride,
+             const void* const* d_expected_ptr, bool by_ptr, uint64_t count, photon_crc_verify_report* d_report,
+             uint64_t* d_bad_idx, uint64_t bad_cap, void* d_work, uint64_t work_bytes, void* stream) {
+    typedef typename W::T T;
+    if (!count) return 0;
+    if (!d_crc || (by_ptr ? !d_expected_ptr : !d_expected) || !d_report || !d_work || (!d_bad_idx && bad_cap))
+        return fail(-EINVAL, by_ptr ? "null computed CRCs, pointer array, report, workspace or index list"
+                                    : "null computed CRCs, expected words, report, workspace or index list");
+    if (!by_ptr && expected_stride < sizeof(T) && count > 1)
+        return fail(-EINVAL, "expected_stride " + std::to_string(expected_stride) + " is below the word width " +
+                                 std::to_string(sizeof(T)));
+    const uint32_t tile = verify_tile_now();
+    const uint64_t words = verify_work_words(count, tile);
+    if (words == kVerifyNone)
+        return fail(-EINVAL, "too many entries: " + std::to_string(count) + " are more than " +
+                                 std::to_string(kVerifyMaxCount));
+    if (work_bytes < words * 8)
+        return fail(-EINVAL, "workspace too small: work_bytes " + std::to_string(work_bytes) + ", needed " +
+                                 std::to_string(words * 8));
+    if ((uintptr_t)d_work & 7u) return fail(-EINVAL, "the workspace is not 8-byte aligned");
+    int cus = 0;
+    const int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint64_t* work = static_cast<uint64_t*>(d_work);
+    const uint64_t tiles = verify_tiles(count, tile);
+    const dim3 grid(verify_grid(tiles)), block(tile < kVerifyBlock ? tile : kVerifyBlock);
+    hipLaunchKernelGGL(verify_mark_kernel<T>, grid, block, 0, st, d_crc, d_expected, expected_stride, d_expected_ptr,
+                       count, tile, work);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, W::kKernel, " verify_mark_kernel launch");
+    hipLaunchKernelGGL(verify_scan_kernel, dim3(1), dim3(kVerifyScanBlock), 0, st, work, tiles, bad_cap,
+                       reinterpret_cast<uint64_t*>(d_report));
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, W::kKernel, " verify_scan_kernel launch");
+    if (!bad_cap) return 0;
+    hipLaunchKernelGGL(verify_list_kernel<T>, grid, block, 0, st, d_crc, d_expected, expected_stride, d_expected_ptr,
+                       count, tile, static_cast<const uint64_t*>(work), bad_cap, d_bad_idx);
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, " verify_list_kernel launch");
+}
+
+// photon_crc32c_stamp_n / _stamp_ptr_n and the CRC-64 forms.
+template <typename W>
+int stamp_n(const typename W::T* d_crc, uint64_t count, void* d_dst, uint64_t dst_stride, void* const* d_dst_ptr,
+            bool by_ptr, void* stream) {
+    typedef typename W::T T;
+    if (!count) return 0;
+    if (!d_crc || (by_ptr ? !d_dst_ptr : !d_dst))
+        return fail(-EINVAL, by_ptr ? "null CRCs or pointer array" : "null CRCs or destination");
+    if (!by_ptr && dst_stride < sizeof(T) && count > 1)
+        return fail(-EINVAL, "dst_stride " + std::to_string(dst_stride) + " is below the word width " +
+                                 std::to_string(sizeof(T)));
+    if (count > kVerifyMaxCount)
+        return fail(-EINVAL, "too many entries: " + std::to_string(count) + " are more than " +
+                                 std::to_string(kVerifyMaxCount));
+    int cus = 0;
+    const int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    hipLaunchKernelGGL(verify_stamp_kernel<T>, dim3(verify_grid((count + kVerifyBlock - 1) / kVerifyBlock)),
+                       dim3(kVerifyBlock), 0, static_cast<hipStream_t>(stream), d_crc, count, d_dst, dst_stride,
+                       d_dst_ptr);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, " verify_stamp_kernel launch");
+}
+
 // ------------------------------------------- many large parts
 // The piece of photon_crc{32c,64ecma}_{copy,batch}_parts_n: a multiple of 4
 // KiB, 0 = automatic (photon_crc_set_parts_piece).
@@ -2418,6 +2501,105 @@ int photon_crc_test_fold_parts(int crc64, const void* crc, const uint64_t* len, 
     else
         *result = fold_replay<Gf32>(static_cast<const uint32_t*>(crc), len, count, (uint32_t)seed, nthreads,
                                     pow_table<Crc32c>().x8pow2, total);
+    return 0;
+}
+
+uint64_t photon_crc_verify_work_bytes(uint64_t count) {
+    const uint64_t words = verify_work_words(count, verify_tile_now());
+    return words == kVerifyNone ? ~0ull : words * 8;
+}
+
+int photon_crc32c_verify_n(const uint32_t* d_crc, const void* d_expected, uint64_t expected_stride, uint64_t count,
+                           photon_crc_verify_report* d_report, uint64_t* d_bad_idx, uint64_t bad_cap, void* d_work,
+                           uint64_t work_bytes, void* stream) {
+    return verify_n<Crc32c>(d_crc, d_expected, expected_stride, nullptr, false, count, d_report, d_bad_idx, bad_cap,
+                            d_work, work_bytes, stream);
+}
+
+int photon_crc64ecma_verify_n(const uint64_t* d_crc, const void* d_expected, uint64_t expected_stride,
+                              uint64_t count, photon_crc_verify_report* d_report, uint64_t* d_bad_idx,
+                              uint64_t bad_cap, void* d_work, uint64_t work_bytes, void* stream) {
+    return verify_n<Crc64>(d_crc, d_expected, expected_stride, nullptr, false, count, d_report, d_bad_idx, bad_cap,
+                           d_work, work_bytes, stream);
+}
+
+int photon_crc32c_verify_ptr_n(const uint32_t* d_crc, const void* const* d_expected_ptr, uint64_t count,
+                               photon_crc_verify_report* d_report, uint64_t* d_bad_idx, uint64_t bad_cap,
+                               void* d_work, uint64_t work_bytes, void* stream) {
+    return verify_n<Crc32c>(d_crc, nullptr, 0, d_expected_ptr, true, count, d_report, d_bad_idx, bad_cap, d_work,
+                            work_bytes, stream);
+}
+
+int photon_crc64ecma_verify_ptr_n(const uint64_t* d_crc, const void* const* d_expected_ptr, uint64_t count,
+                                  photon_crc_verify_report* d_report, uint64_t* d_bad_idx, uint64_t bad_cap,
+                                  void* d_work, uint64_t work_bytes, void* stream) {
+    return verify_n<Crc64>(d_crc, nullptr, 0, d_expected_ptr, true, count, d_report, d_bad_idx, bad_cap, d_work,
+                           work_bytes, stream);
+}
+
+int photon_crc32c_stamp_n(const uint32_t* d_crc, uint64_t count, void* d_dst, uint64_t dst_stride, void* stream) {
+    return stamp_n<Crc32c>(d_crc, count, d_dst, dst_stride, nullptr, false, stream);
+}
+
+int photon_crc64ecma_stamp_n(const uint64_t* d_crc, uint64_t count, void* d_dst, uint64_t dst_stride, void* stream) {
+    return stamp_n<Crc64>(d_crc, count, d_dst, dst_stride, nullptr, false, stream);
+}
+
+int photon_crc32c_stamp_ptr_n(const uint32_t* d_crc, uint64_t count, void* const* d_dst_ptr, void* stream) {
+    return stamp_n<Crc32c>(d_crc, count, nullptr, 0, d_dst_ptr, true, stream);
+}
+
+int photon_crc64ecma_stamp_ptr_n(const uint64_t* d_crc, uint64_t count, void* const* d_dst_ptr, void* stream) {
+    return stamp_n<Crc64>(d_crc, count, nullptr, 0, d_dst_ptr, true, stream);
+}
+
+int photon_crc_set_verify_tile(uint32_t entries) {
+    if (entries && !verify_tile_ok(entries))
+        return fail(-EINVAL, "verify tile: 0 (the default) or a power of two from 64 to 65536");
+    g_verify_tile.store(entries, std::memory_order_relaxed);
+    return 0;
+}
+
+// tuning.h: the kernels' three steps (verify_scan.h) on the host.
+int photon_crc_test_verify(int crc64, const void* crc, const void* expected, uint64_t expected_stride,
+                           const void* const* expected_ptr, uint64_t count, uint32_t tile, uint64_t bad_cap,
+                           uint64_t report[4], uint64_t* bad_idx) {
+    if (!count || !crc || (!expected && !expected_ptr) || !report || (!bad_idx && bad_cap))
+        return fail(-EINVAL, "null argument or no entries");
+    if (!verify_tile_ok(tile) || count > kVerifyMaxCount) return fail(-EINVAL, "bad tile or too many entries");
+    std::vector<uint64_t> work(verify_work_words(count, tile), 0xA5A5A5A5A5A5A5A5ull);
+    if (crc64)
+        verify_replay<uint64_t>(static_cast<const uint64_t*>(crc), expected, expected_stride, expected_ptr, count, tile,
+                                bad_cap, work.data(), report, bad_idx);
+    else
+        verify_replay<uint32_t>(static_cast<const uint32_t*>(crc), expected, expected_stride, expected_ptr, count, tile,
+                                bad_cap, work.data(), report, bad_idx);
+    return 0;
+}
+
+// tuning.h, bench only: what a caller did before the verify calls existed.
+int photon_crc_util_verify_on_host(int crc64, const void* d_crc, void* h_crc, const void* h_expected, uint64_t count,
+                                   uint64_t report[4], uint64_t* h_bad_idx, uint64_t bad_cap, void* stream) {
+    if (!d_crc || !h_crc || !h_expected || !report || (!h_bad_idx && bad_cap)) return fail(-EINVAL, "null argument");
+    if (int rc = photon_crc_stream_sync(stream)) return rc;
+    const size_t w = crc64 ? 8 : 4;
+    const hipError_t e = hipMemcpy(h_crc, d_crc, count * w, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
+    uint64_t nbad = 0, first = ~0ull;
+    auto loop = [&](auto* c, auto* x) {
+        for (uint64_t i = 0; i < count; ++i) {
+            if (c[i] == x[i]) continue;
+            if (!nbad) first = i;
+            if (nbad < bad_cap) h_bad_idx[nbad] = i;
+            ++nbad;
+        }
+    };
+    if (crc64) loop(static_cast<const uint64_t*>(h_crc), static_cast<const uint64_t*>(h_expected));
+    else loop(static_cast<const uint32_t*>(h_crc), static_cast<const uint32_t*>(h_expected));
+    report[0] = nbad;
+    report[1] = first;
+    report[2] = nbad < bad_cap ? nbad : bad_cap;
+    report[3] = count;
     return 0;
 }
 

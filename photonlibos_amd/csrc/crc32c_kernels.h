@@ -11,6 +11,7 @@
 #include "fold_parts.h"
 #include "gf2.h"
 #include "parts_plan.h"
+#include "verify_scan.h"
 
 #ifndef PCRC_LANE_SEL
 #define PCRC_LANE_SEL 1  // per-lane v_perm selectors instead of rotating the word (+0.3 % on C2)
@@ -1701,6 +1702,150 @@ __global__ __launch_bounds__(kFoldMaxBlock) void crc32c_fold_parts_kernel(const 
                                                                           const uint32_t* seeds, uint32_t* out,
                                                                           uint64_t* total, PowTable pt) {
     fold_parts_block<Gf32>(crc, len, obj_start, nobj, nparts, seed0, seeds, out, total, pt.x8pow2);
+}
+
+// ------------------------------------------- stored CRCs checked on the device
+// photon_crc32c_verify_n / _verify_ptr_n / _stamp_n / _stamp_ptr_n and the
+// CRC-64 forms, T = the CRC word: the three steps of
+// verify_scan.h. A wavefront takes a row of 64 consecutive entries, a
+// workgroup of blockDim.x = min(tile, kVerifyBlock) threads a tile, blockDim.x
+// entries at a time; the rows' masks are 64-bit __ballots. Plain loads and
+// stores only; a launch writes the workspace words of its own tiles (mark,
+// scan), the report (scan) and bad_idx[0 .. nlisted) (list), nothing else.
+template <typename T>
+__global__ __launch_bounds__(kVerifyBlock) void verify_mark_kernel(const T* crc, const void* expected, uint64_t stride,
+                                                                   const void* const* expected_ptr, uint64_t count,
+                                                                   uint32_t tile, uint64_t* work) {
+    __shared__ VerifyTile part[kVerifyBlock / 64];
+    const uint64_t tiles = verify_tiles(count, tile);
+    const uint32_t t = threadIdx.x, nt = blockDim.x, w = t >> 6, l = t & 63u;
+    for (uint64_t k = blockIdx.x; k < tiles; k += gridDim.x) {
+        const uint64_t lo = k * tile, hi = count - lo < tile ? count : lo + tile;
+        VerifyTile mine = verify_tile_none();  // this wavefront's rows, in index order; the same on its lanes
+        for (uint64_t row = lo + 64u * w; row < hi; row += nt) {
+            const uint32_t e = row + l < hi ? verify_entry<T>(crc, expected, stride, expected_ptr, row + l) : 0u;
+            verify_row_add(&mine, row, __ballot(e >> 1), __ballot(e & 1u));
+        }
+        if (l == 0) part[w] = mine;
+        __syncthreads();
+        if (t == 0) {
+            VerifyTile all = part[0];
+            for (uint32_t v = 1; v < nt / 64; ++v) {
+                all.nbad += part[v].nbad;
+                all.ncmp += part[v].ncmp;
+                all.first = part[v].first < all.first ? part[v].first : all.first;
+            }
+            work[k] = all.nbad;
+            work[tiles + k] = all.ncmp;
+            work[2 * tiles + k] = all.first;
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ uint64_t wave_shfl_up(uint64_t v, uint32_t d) {
+    return (uint64_t)__shfl_up((unsigned long long)v, d, 64);
+}
+__device__ __forceinline__ uint64_t wave_shfl_xor(uint64_t v, uint32_t d) {
+    return (uint64_t)__shfl_xor((unsigned long long)v, (int)d, 64);
+}
+
+// One workgroup of kVerifyScanBlock threads: a chunk of that many tiles at a
+// time, thread t the tile chunk + t; the chunk's exclusive sums by shuffles in
+// the wavefront and the wavefronts' totals through LDS, on top of the 64-bit
+// carry of the chunks before (verify_scan_step, all of a chunk's at once).
+__global__ __launch_bounds__(kVerifyScanBlock) void verify_scan_kernel(uint64_t* work, uint64_t tiles,
+                                                                       uint64_t bad_cap, uint64_t* report) {
+    constexpr uint32_t NW = kVerifyScanBlock / 64;
+    __shared__ uint64_t wsum[NW], wcmp[NW], wfirst[NW];
+    const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63u;
+    uint64_t carry = 0;                      // bad entries of the chunks before: the same on every thread
+    uint64_t ncmp = 0, first = kVerifyNone;  // over this thread's tiles
+    for (uint64_t c0 = 0; c0 < tiles; c0 += kVerifyScanBlock) {
+        const uint64_t k = c0 + t;
+        uint64_t n = 0;
+        if (k < tiles) {
+            n = work[k];
+            ncmp += work[tiles + k];
+            const uint64_t f = work[2 * tiles + k];
+            first = f < first ? f : first;
+        }
+        uint64_t inc = n;  // the inclusive sum over the wavefront
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint64_t v = wave_shfl_up(inc, d);
+            if (l >= d) inc += v;
+        }
+        if (l == 63) wsum[w] = inc;
+        __syncthreads();
+        uint64_t before = 0, total = 0;
+        for (uint32_t v = 0; v < NW; ++v) {
+            before += v < w ? wsum[v] : 0ull;
+            total += wsum[v];
+        }
+        if (k < tiles) work[k] = carry + before + inc - n;
+        carry += total;
+        __syncthreads();
+    }
+    for (uint32_t d = 32; d; d >>= 1) {
+        ncmp += wave_shfl_xor(ncmp, d);
+        const uint64_t f = wave_shfl_xor(first, d);
+        first = f < first ? f : first;
+    }
+    if (l == 0) {
+        wcmp[w] = ncmp;
+        wfirst[w] = first;
+    }
+    __syncthreads();
+    if (t == 0) {
+        VerifyScan s = {carry, 0, kVerifyNone};
+        for (uint32_t v = 0; v < NW; ++v) {
+            s.ncmp += wcmp[v];
+            s.first = wfirst[v] < s.first ? wfirst[v] : s.first;
+        }
+        verify_report_store(report, s, bad_cap);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kVerifyBlock) void verify_list_kernel(const T* crc, const void* expected, uint64_t stride,
+                                                                   const void* const* expected_ptr, uint64_t count,
+                                                                   uint32_t tile, const uint64_t* work,
+                                                                   uint64_t bad_cap, uint64_t* bad_idx) {
+    __shared__ uint32_t wbad[kVerifyBlock / 64];
+    const uint64_t tiles = verify_tiles(count, tile);
+    const uint32_t t = threadIdx.x, nt = blockDim.x, w = t >> 6, l = t & 63u;
+    for (uint64_t k = blockIdx.x; k < tiles; k += gridDim.x) {
+        if (!verify_tile_listed(work, tiles, k, bad_cap)) continue;  // the same on every thread
+        const uint64_t lo = k * tile, hi = count - lo < tile ? count : lo + tile;
+        uint64_t at = work[k];  // where the step's first bad entry goes
+        for (uint64_t base = verify_list_start(lo, work[2 * tiles + k], nt); base < hi && at < bad_cap; base += nt) {
+            const uint64_t i = base + t;
+            const uint32_t e = i < hi ? verify_entry<T>(crc, expected, stride, expected_ptr, i) : 0u;
+            const uint64_t bad = __ballot(e >> 1);
+            if (l == 0) wbad[w] = (uint32_t)__builtin_popcountll(bad);
+            __syncthreads();
+            uint32_t before = 0, total = 0;
+            for (uint32_t v = 0; v < nt / 64; ++v) {
+                before += v < w ? wbad[v] : 0u;
+                total += wbad[v];
+            }
+            const uint64_t pos = at + before + verify_rank(bad, l);
+            if ((e >> 1) && pos < bad_cap) bad_idx[pos] = i;
+            at += total;
+            __syncthreads();
+        }
+    }
+}
+
+// stamp: word i, little-endian, at dst + i * stride or dst_ptr[i] (null: skipped).
+template <typename T>
+__global__ __launch_bounds__(kVerifyBlock) void verify_stamp_kernel(const T* crc, uint64_t count, void* dst,
+                                                                    uint64_t stride, void* const* dst_ptr) {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += step) {
+        void* p = dst_ptr ? dst_ptr[i] : static_cast<void*>(static_cast<char*>(dst) + i * stride);
+        if (p) verify_store<T>(p, crc[i]);
+    }
 }
 
 // ------------------------------------------- many large parts, each cut over the chip

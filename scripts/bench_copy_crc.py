@@ -75,6 +75,22 @@ the ratio (b)/(a), and the spread between the alternations of each arm;
                     the CPU replay of the kernel are compared before anything is timed.
                     "faster_3x" is true when host - device exceeds three times the spread
                     between host's alternations. --out appends.
+  --verify : stored CRCs checked on the device (photon_crc32c_verify_n and
+                    photon_crc64ecma_verify_n, both in one run), the same alternations, one JSON
+                    line per CRC and row (65,536 and 1,048,576 entries with 0 and 3 bad ones,
+                    bad_cap 64, and 1,048,576 with 1 % bad, bad_cap = the count; dense expected
+                    words): "host" = the route before the calls existed, natively
+                    (photon_crc_util_verify_on_host: photon_crc_stream_sync, the CRC words copied
+                    to pinned host memory, a compare loop against a host array), wall clock in us
+                    from the call to the verdict in hand; "device" = the new call with report and
+                    list in pinned host memory, wall clock from the launch to the stream sync;
+                    "device_kernels" = its three launches alone by HIP events. Both arms' reports
+                    and lists are compared with the expected ones before anything is timed.
+                    "faster_3x" is true when host - device exceeds three times the spread between
+                    host's alternations. --tiles 1024,4096,... measures those tiles in place of the
+                    default (photon_crc_set_verify_tile); with the default alone, two more lines
+                    give the C2 batch alone against the batch followed by verify_n, by events.
+                    --out appends.
   --parts : copy + CRC of many large parts in one launch
                     (photon_crc32c_copy_parts_n; with --crc64 the CRC-64 call), the same method,
                     device to device, the parts back to back from buf+1 to dbuf+1 (co-aligned):
@@ -118,6 +134,8 @@ ap.add_argument("--long", action="store_true")
 ap.add_argument("--sizes", default="64,256,1024", help="--long: payload sizes in MiB")
 ap.add_argument("--fold", action="store_true")
 ap.add_argument("--parts", action="store_true")
+ap.add_argument("--verify", action="store_true")
+ap.add_argument("--tiles", default="0", help="--verify: tiles in entries to measure, 0 = the default")
 ap.add_argument("--tree", default="working tree", help="--fold: a label of the tree measured, written to each line")
 args = ap.parse_args()
 
@@ -575,6 +593,126 @@ def bench_fold(crc64, nobj, per):
     return res
 
 
+VERIFY_ROWS = [(65536, "0"), (65536, "3"), (1 << 20, "0"), (1 << 20, "3"), (1 << 20, "1%")]  # entries, bad ones
+
+
+def bench_verify(crc64, count, bad, tile):
+    """(a) photon_crc_util_verify_on_host against (b) verify_n with report and list in pinned memory."""
+    import time
+    rng = np.random.default_rng(0x7E21F + count)
+    wdt = np.uint64 if crc64 else np.uint32
+    crcs = rng.integers(0, 1 << 63, count, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    crcs = crcs if crc64 else (crcs >> np.uint64(32)).astype(np.uint32)
+    if bad == "1%":
+        hit = np.nonzero(rng.random(count) < 0.01)[0]
+    else:
+        hit = np.array([17, count // 2 + 1, count - 1][:int(bad)], np.int64)
+    cap = count if bad == "1%" else 64
+    exp = crcs.copy()
+    exp[hit] ^= wdt(0x80000001)
+    sdt = torch.int64 if crc64 else torch.int32
+    d_crc = torch.from_numpy(crcs.view(np.int64 if crc64 else np.int32)).cuda()
+    d_exp = torch.from_numpy(exp.view(np.int64 if crc64 else np.int32)).cuda()
+    h_crc = torch.zeros(count, dtype=sdt).pin_memory()  # (a)'s landing buffer for the CRC words
+    rep_b = torch.zeros(4, dtype=torch.int64).pin_memory()  # in hand after the sync
+    lst_b = torch.zeros(cap, dtype=torch.int64).pin_memory()
+    rep_a, lst_a = np.zeros(4, np.uint64), np.zeros(cap, np.uint64)
+    ck.set_verify_tile(tile)
+    work = torch.empty(ck.verify_work_bytes(count), dtype=torch.uint8, device="cuda")
+    verify = ck.verify64_device if crc64 else ck.verify_device
+    sh = st.cuda_stream
+
+    def host():    # (a): sync, CRC words to the host, a compare loop on the host
+        ck._check(lib().photon_crc_util_verify_on_host(int(crc64), d_crc.data_ptr(), h_crc.data_ptr(),
+                                                       exp.ctypes.data, count, rep_a.ctypes.data, lst_a.ctypes.data,
+                                                       cap, sh))
+
+    def launch():
+        verify(d_crc, d_exp, 8 if crc64 else 4, count, rep_b, lst_b, cap, work, stream=st)
+
+    def device():  # (b): the launches, then the stream sync that returns report and list
+        launch()
+        ck._check(lib().photon_crc_stream_sync(sh))
+
+    torch.cuda.synchronize()
+    host()
+    device()
+    want = [hit.size, int(hit[0]) if hit.size else (1 << 64) - 1, min(hit.size, cap), count]
+    got = rep_b.numpy().view(np.uint64)
+    assert list(rep_a) == want and list(got) == want, f"the reports differ: {rep_a} {got} {want}"
+    assert np.array_equal(lst_a[:hit.size], hit) and np.array_equal(lst_b.numpy()[:hit.size], hit), "the lists differ"
+    arms = {"host": host, "device": device}
+    times = {"host": [], "device": [], "device_kernels": []}
+    means = {k: [] for k in times}
+    for r in range(args.rounds):
+        for name in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+            fn = arms[name]
+            for _ in range(args.warmup):
+                fn()
+            t = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e6)
+            times[name] += t
+            means[name].append(float(np.mean(t)))
+            if name == "device":  # the three kernels alone, by events on the launch stream
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.reps + 1)]
+                ev[0].record(st)
+                for k in range(args.reps):
+                    launch()
+                    ev[k + 1].record(st)
+                torch.cuda.synchronize()
+                t = [ev[k].elapsed_time(ev[k + 1]) * 1e3 for k in range(args.reps)]
+                times["device_kernels"] += t
+                means["device_kernels"].append(float(np.mean(t)))
+    ck.set_verify_tile(0)
+    res = {"shape": "verify", "crc": "crc64ecma" if crc64 else "crc32c", "entries": count, "bad": int(hit.size),
+           "bad_cap": cap, "tile": tile or "default", "tiles": -(-count // (tile or 1024)), "tree": args.tree,
+           "rounds": args.rounds, "reps": args.reps, "warmup": args.warmup}
+    for name in times:
+        us = np.asarray(times[name])
+        res[name] = {"us_mean": round(float(us.mean()), 3), "us_median": round(float(np.median(us)), 3),
+                     "round_means_us": [round(m, 3) for m in means[name]],
+                     "spread_us": round(max(means[name]) - min(means[name]), 3)}
+    a, b = res["host"]["us_mean"], res["device"]["us_mean"]
+    res["ratio_device_over_host"] = round(b / a, 4)
+    res["margin_over_host_spread"] = round((a - b) / max(res["host"]["spread_us"], 1e-9), 2)
+    res["faster_3x"] = bool(a - b > 3 * res["host"]["spread_us"])
+    return res
+
+
+def bench_verify_after_batch(crc64):
+    """The C2 batch alone against the batch followed by verify_n on the same stream, by events."""
+    nbytes, count = SHAPES["c2"]
+    buf = torch.empty(nbytes * count, dtype=torch.uint8, device="cuda")
+    ck.fill_splitmix(buf, nbytes, nbytes, count, 0x5EED0001)
+    sdt = torch.int64 if crc64 else torch.int32
+    out, stored = torch.zeros(count, dtype=sdt, device="cuda"), torch.zeros(count, dtype=sdt, device="cuda")
+    rep = torch.zeros(4, dtype=torch.int64).pin_memory()
+    lst = torch.zeros(64, dtype=torch.int64).pin_memory()
+    work = torch.empty(ck.verify_work_bytes(count), dtype=torch.uint8, device="cuda")
+    batch = ck.batch64_strided if crc64 else ck.batch_strided
+    verify = ck.verify64_device if crc64 else ck.verify_device
+    batch(buf, nbytes, nbytes, count, stored, stream=st)  # the stored words: none is bad
+
+    def alone():
+        batch(buf, nbytes, nbytes, count, out, stream=st)
+
+    def with_verify():
+        batch(buf, nbytes, nbytes, count, out, stream=st)
+        verify(out, stored, 8 if crc64 else 4, count, rep, lst, 64, work, stream=st)
+
+    with_verify()
+    torch.cuda.synchronize()
+    assert list(rep.numpy().view(np.uint64)) == [0, (1 << 64) - 1, 0, count], rep
+    res = {"shape": "verify_after_c2_batch", "crc": "crc64ecma" if crc64 else "crc32c", "nbytes": nbytes,
+           "count": count, "tree": args.tree, "rounds": args.rounds, "reps": args.reps, "warmup": args.warmup}
+    res.update(alternate({"batch": alone, "batch_verify": with_verify}))
+    res["added_us"] = round((res["batch_verify"]["ms_mean"] - res["batch"]["ms_mean"]) * 1e3, 3)
+    return res
+
+
 def alternate(arms):
     """The §4.3 protocol over callables: --rounds alternations of --reps timed calls after --warmup each."""
     means = {k: [] for k in arms}
@@ -750,6 +888,19 @@ if args.parts:
         if args.shapes != "c2,c3" and shape not in args.shapes.split(","):
             continue
         line = json.dumps(bench_parts(shape, what))
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+    sys.exit(0)
+
+if args.verify:
+    plan = [(bench_verify, (c64, count, bad, int(tile))) for tile in args.tiles.split(",") for c64 in (False, True)
+            for count, bad in VERIFY_ROWS]
+    if args.tiles == "0":
+        plan += [(bench_verify_after_batch, (c64,)) for c64 in (False, True)]
+    for fn, a in plan:
+        line = json.dumps(fn(*a))
         print(line, flush=True)
         if args.out:
             with open(args.out, "a") as f:
