@@ -578,6 +578,59 @@ int photon_crc64ecma_fold_parts_n(const uint64_t* d_crc, const uint64_t* d_len,
                                   uint64_t seed0, const uint64_t* d_seeds,
                                   uint64_t* d_out, uint64_t* d_total, void* stream);
 
+/* The running CRCs of objects over their parts: photon_crc32c_fold_parts_n /
+ * photon_crc64ecma_fold_parts_n with every intermediate value kept. Inputs as
+ * the fold's: nparts (CRC from seed 0, 64-bit length) pairs, d_obj_start with
+ * nobj + 1 entries or null for ONE object of all parts (nobj must then be 1),
+ * seed_m = d_seeds ? d_seeds[m] : seed0. For object m over its parts s in
+ * order, with A = seed_m and E = 0:
+ *     A = A * x^(8 * d_len[s]) ^ d_crc[s];   d_run[s] = A;
+ *     E += d_len[s];                         d_end[s] = E;   (optional; mod 2^64)
+ * -- the fold's linear definition (the same remark about a part of length 0
+ * with a non-zero CRC), so the last entry of every non-empty object is
+ * bit-identical to the fold's d_out[m] and d_total[m] on the same inputs. For
+ * part CRCs over real bytes d_run[s] = crc32c_extend / crc64ecma_extend of
+ * the object's bytes through part s from seed_m: the value
+ * x-oss-hash-crc64ecma carries after that append (ecosystem/oss.cpp:1271-1298),
+ * and d_end[s] is the next append's position. An empty object writes nothing
+ * (its CRC is its seed). Any range of whole parts follows from two running
+ * values through photon_crc32c_trim_batch.
+ *   - nobj == 0 or nparts == 0 returns 0 and touches nothing.
+ *   - A null d_crc, d_len, d_run or d_work, or a null d_obj_start with
+ *     nobj != 1, gives -EINVAL ("null ..." in photon_crc_last_error()).
+ *   - d_work: device memory of at least photon_crc_scan_work_bytes(nparts)
+ *     bytes (work_bytes says how many it has), 8-byte aligned; it needs no
+ *     clearing and keeps nothing between calls. A work_bytes too small gives
+ *     -EINVAL (both numbers in the error text), and so does an nparts for
+ *     which photon_crc_scan_work_bytes returns ~0 (more than 2^40 parts).
+ *   - d_obj_start must be non-decreasing, start at 0 and end at nparts (the
+ *     caller's duty). If it does not, the values are unspecified, but no entry
+ *     outside [0, nparts) of any array (and none outside d_obj_start[0..nobj),
+ *     d_seeds[0..nobj)) is read or written.
+ *   - d_run and d_end must not overlap the inputs (not checked).
+ * All arrays are device-accessible memory; d_len and d_obj_start may be
+ * pinned host memory. Asynchronous on `stream`. The calls allocate nothing and
+ * synchronise nothing and write with plain stores only: no atomics, no
+ * memset, no per-stream state; every workspace word a call reads, that call
+ * wrote -- the result is deterministic, a call is capturable into a graph and
+ * replayable, and calls may run concurrently with distinct d_run / d_end /
+ * d_work. No CPU fallback. A segmented scan in tiles of the index space,
+ * whatever objects a tile holds: one object of N parts is
+ * spread over about N / tile workgroups. At most three launches (reduce the
+ * tiles, carry across them, apply); one when everything is one tile. */
+uint64_t photon_crc_scan_work_bytes(uint64_t nparts);
+
+int photon_crc32c_scan_parts_n(const uint32_t* d_crc, const uint64_t* d_len,
+                               const uint64_t* d_obj_start, uint64_t nobj, uint64_t nparts,
+                               uint32_t seed0, const uint32_t* d_seeds,
+                               uint32_t* d_run, uint64_t* d_end,
+                               void* d_work, uint64_t work_bytes, void* stream);
+int photon_crc64ecma_scan_parts_n(const uint64_t* d_crc, const uint64_t* d_len,
+                                  const uint64_t* d_obj_start, uint64_t nobj, uint64_t nparts,
+                                  uint64_t seed0, const uint64_t* d_seeds,
+                                  uint64_t* d_run, uint64_t* d_end,
+                                  void* d_work, uint64_t work_bytes, void* stream);
+
 /* Check stored CRCs on the device: the step after any call above that left
  * `count` computed words in d_crc, on the same stream, with nothing in
  * between. Entry i is BAD when d_crc[i] differs from its expected word.

@@ -220,6 +220,39 @@ int photon_crc_test_fold_parts(int crc64, const void* crc, const uint64_t* len, 
 int photon_crc_util_fold_on_host(int crc64, const void* d_crc, const uint64_t* h_len, const uint64_t* h_obj_start,
                                  uint64_t nobj, uint64_t nparts, uint64_t seed, void* h_out, void* stream);
 
+/* Tile of photon_crc32c_scan_parts_n / photon_crc64ecma_scan_parts_n in
+ * entries (testing / tuning): 0 = the default (1,024), else
+ * a power of two from 64 to 65,536. It sets the tile count and so
+ * photon_crc_scan_work_bytes: size the workspace after setting it. */
+int photon_crc_set_scan_tile(uint32_t entries);
+
+/* The scan calls' geometry, for tests to derive their sizes from: out[0] =
+ * the current tile in entries, out[1] = the tiles per chunk of the carry
+ * step, out[2] = the most workgroups of a reduce / apply launch (tiles beyond
+ * them are walked by a stride loop). */
+void photon_crc_test_scan_geometry(uint64_t out[3]);
+
+/* CPU replay of the scan kernels (photonlibos_amd/csrc/scan_parts.h): the
+ * reduce, carry and apply steps run on host arrays for tiles of `tile`
+ * entries and workgroups of `nthreads` threads. crc[], seeds[] and run[] are
+ * uint64_t words if crc64, else uint32_t; the other arguments as
+ * photon_crc32c_scan_parts_n's (end may be null). Returns 0, or -EINVAL (a
+ * null argument, no threads, a bad tile). */
+int photon_crc_test_scan_parts(int crc64, const void* crc, const uint64_t* len, const uint64_t* obj_start,
+                               uint64_t nobj, uint64_t nparts, uint64_t seed0, const void* seeds, uint32_t tile,
+                               uint32_t nthreads, void* run, uint64_t* end);
+
+/* Bench utility (scripts/bench_copy_crc.py --scan, arm (a)): the route a
+ * caller took before the scan calls existed, natively:
+ * photon_crc_stream_sync(stream), the nparts part CRCs at d_crc copied into
+ * the caller's host buffer h_crc (pinned, for the fastest copy), per object a
+ * serial crc32c_combine / crc64ecma_combine chain from `seed` over the host
+ * arrays h_len / h_obj_start (lengths below 4 GiB) into h_run (pinned), and
+ * h_run copied to d_run (uint32_t or, if crc64, uint64_t words). Synchronous. */
+int photon_crc_util_scan_on_host(int crc64, const void* d_crc, void* h_crc, const uint64_t* h_len,
+                                 const uint64_t* h_obj_start, uint64_t nobj, uint64_t nparts, uint64_t seed,
+                                 void* h_run, void* d_run, void* stream);
+
 /* Tile of photon_crc32c_verify_n / _verify_ptr_n and the CRC-64 forms in
  * entries (testing / tuning): 0 = the default (1,024), else
  * a power of two from 64 to 65,536. It sets the tile count and so

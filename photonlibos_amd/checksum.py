@@ -37,6 +37,7 @@ __all__ = [
     "set_parts_piece",
     "series64_device", "combine_series64_device", "fold_parts_device", "fold_parts64_device",
     "crc64ecma_series_at", "crc64ecma_combine_series_at",
+    "scan_work_bytes", "set_scan_tile", "scan_parts_device", "scan_parts64_device",
     "VerifyReport", "verify_work_bytes", "set_verify_tile",
     "verify_device", "verify64_device", "verify_ptr_device", "verify64_ptr_device",
     "stamp_device", "stamp64_device", "stamp_ptr_device", "stamp64_ptr_device",
@@ -598,6 +599,36 @@ def fold_parts64_device(crcs, lens, obj_start, nobj, nparts, out, seed=0, seeds=
     _check(lib().photon_crc64ecma_fold_parts_n(_ptr(crcs), _ptr(lens), _ptr(obj_start), nobj, nparts,
                                                seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(out), _ptr(total),
                                                _stream(stream)))
+
+
+def scan_work_bytes(nparts):
+    """Bytes of workspace scan_parts*_device needs for `nparts` parts under the current tile (set_scan_tile)."""
+    return lib().photon_crc_scan_work_bytes(nparts)
+
+
+def set_scan_tile(entries):
+    """Tile of the scan calls: 0 = the default (1,024), else a power of two from 64 to 65,536 (tuning.h)."""
+    _check(lib().photon_crc_set_scan_tile(entries))
+
+
+def scan_parts_device(crcs, lens, obj_start, nobj, nparts, run, work, work_bytes=None, seed=0, seeds=None, end=None,
+                      stream=None):
+    """The running CRC-32Cs of objects over their parts, on the device: inputs as fold_parts_device;
+    run[s] (uint32) = the fold of the object's parts up to and including s from seeds[m] or seed, end[s]
+    (optional, uint64) = the object's bytes through part s. The last entry of an object is what
+    fold_parts_device gives; an empty object writes nothing. work: device workspace of at least
+    scan_work_bytes(nparts) bytes (work_bytes, or the tensor's size). Async, capturable."""
+    _check(lib().photon_crc32c_scan_parts_n(_ptr(crcs), _ptr(lens), _ptr(obj_start), nobj, nparts,
+                                            seed & 0xFFFFFFFF, _ptr(seeds), _ptr(run), _ptr(end), _ptr(work),
+                                            _work_bytes(work, work_bytes), _stream(stream)))
+
+
+def scan_parts64_device(crcs, lens, obj_start, nobj, nparts, run, work, work_bytes=None, seed=0, seeds=None,
+                        end=None, stream=None):
+    """scan_parts_device for CRC-64/ECMA (uint64 crcs / seeds / run). Async, capturable."""
+    _check(lib().photon_crc64ecma_scan_parts_n(_ptr(crcs), _ptr(lens), _ptr(obj_start), nobj, nparts,
+                                               seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(run), _ptr(end),
+                                               _ptr(work), _work_bytes(work, work_bytes), _stream(stream)))
 
 
 class VerifyReport(ctypes.Structure):

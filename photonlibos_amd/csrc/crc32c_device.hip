@@ -1597,6 +1597,59 @@ int fold_parts_n(const typename W::T* d_crc, const uint64_t* d_len, const uint64
     return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, "_fold_parts_kernel launch");
 }
 
+// ------------------------------------- running CRCs of an object's parts
+// The tile of the scan calls in entries: a power of two, 0 = the default
+// (photon_crc_set_scan_tile).
+std::atomic<uint32_t> g_scan_tile{0};
+// 1,024: verify's
+constexpr uint32_t kScanTileDefault = 1024;
+
+uint32_t scan_tile_now() {
+    const uint32_t t = g_scan_tile.load(std::memory_order_relaxed);
+    return t ? t : kScanTileDefault;
+}
+
+// photon_crc32c_scan_parts_n / photon_crc64ecma_scan_parts_n: reduce, carry
+// and apply on `stream`; apply alone when everything is one tile.
+template <typename W>
+int scan_parts_n(const typename W::T* d_crc, const uint64_t* d_len, const uint64_t* d_obj_start, uint64_t nobj,
+                 uint64_t nparts, typename W::T seed0, const typename W::T* d_seeds, typename W::T* d_run,
+                 uint64_t* d_end, void* d_work, uint64_t work_bytes, void* stream) {
+    typedef typename W::T T;
+    typedef typename W::Pow P;
+    if (!nobj || !nparts) return 0;
+    if (!d_crc || !d_len || !d_run || !d_work) return fail(-EINVAL, "null part CRCs, lengths, running CRCs or workspace");
+    if (!d_obj_start && nobj != 1) return fail(-EINVAL, "a null d_obj_start means one object: nobj must be 1");
+    const uint32_t tile = scan_tile_now();
+    const uint64_t words = scan_work_words(nparts, tile);
+    if (words == kScanNone)
+        return fail(-EINVAL, "too many parts: " + std::to_string(nparts) + " are more than " +
+                                 std::to_string(kScanMaxParts));
+    if (work_bytes < words * 8)
+        return fail(-EINVAL, "workspace too small: work_bytes " + std::to_string(work_bytes) + ", needed " +
+                                 std::to_string(words * 8));
+    if ((uintptr_t)d_work & 7u) return fail(-EINVAL, "the workspace is not 8-byte aligned");
+    int cus = 0;
+    const int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint64_t* work = static_cast<uint64_t*>(d_work);
+    const ScanIn<T> in = {d_crc, d_len, d_obj_start, nobj, nparts, seed0, d_seeds};
+    const uint64_t tiles = scan_tiles(nparts, tile);
+    const dim3 grid(tiles < kScanMaxGrid ? (uint32_t)tiles : kScanMaxGrid), block(scan_block(tile));
+    hipError_t e;
+    if (tiles > 1) {
+        hipLaunchKernelGGL((scan_reduce_kernel<W, P>), grid, block, 0, st, in, tile, work, pow_table<W>());
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, W::kKernel, " scan_reduce_kernel launch");
+        hipLaunchKernelGGL(scan_carry_kernel<W>, dim3(1), dim3(kScanChunk), 0, st, work, tiles);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, W::kKernel, " scan_carry_kernel launch");
+    }
+    hipLaunchKernelGGL((scan_apply_kernel<W, P>), grid, block, 0, st, in, tile, static_cast<const uint64_t*>(work),
+                       d_run, d_end, pow_table<W>());
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, " scan_apply_kernel launch");
+}
+
 // ------------------------------------- stored CRCs checked on the device
 // The tile of the verify calls in entries: a power of two, 0 = the default
 // (photon_crc_set_verify_tile).
@@ -2502,6 +2555,85 @@ int photon_crc_test_fold_parts(int crc64, const void* crc, const uint64_t* len, 
         *result = fold_replay<Gf32>(static_cast<const uint32_t*>(crc), len, count, (uint32_t)seed, nthreads,
                                     pow_table<Crc32c>().x8pow2, total);
     return 0;
+}
+
+uint64_t photon_crc_scan_work_bytes(uint64_t nparts) {
+    const uint64_t words = scan_work_words(nparts, scan_tile_now());
+    return words == kScanNone ? ~0ull : words * 8;
+}
+
+int photon_crc32c_scan_parts_n(const uint32_t* d_crc, const uint64_t* d_len, const uint64_t* d_obj_start,
+                               uint64_t nobj, uint64_t nparts, uint32_t seed0, const uint32_t* d_seeds,
+                               uint32_t* d_run, uint64_t* d_end, void* d_work, uint64_t work_bytes, void* stream) {
+    return scan_parts_n<Crc32c>(d_crc, d_len, d_obj_start, nobj, nparts, seed0, d_seeds, d_run, d_end, d_work,
+                                work_bytes, stream);
+}
+
+int photon_crc64ecma_scan_parts_n(const uint64_t* d_crc, const uint64_t* d_len, const uint64_t* d_obj_start,
+                                  uint64_t nobj, uint64_t nparts, uint64_t seed0, const uint64_t* d_seeds,
+                                  uint64_t* d_run, uint64_t* d_end, void* d_work, uint64_t work_bytes, void* stream) {
+    return scan_parts_n<Crc64>(d_crc, d_len, d_obj_start, nobj, nparts, seed0, d_seeds, d_run, d_end, d_work,
+                               work_bytes, stream);
+}
+
+int photon_crc_set_scan_tile(uint32_t entries) {
+    if (entries && !scan_tile_ok(entries))
+        return fail(-EINVAL, "scan tile: 0 (the default) or a power of two from 64 to 65536");
+    g_scan_tile.store(entries, std::memory_order_relaxed);
+    return 0;
+}
+
+void photon_crc_test_scan_geometry(uint64_t out[3]) {
+    out[0] = scan_tile_now();
+    out[1] = kScanChunk;
+    out[2] = kScanMaxGrid;
+}
+
+// tuning.h: the kernels' three steps (scan_parts.h) on the host.
+int photon_crc_test_scan_parts(int crc64, const void* crc, const uint64_t* len, const uint64_t* obj_start,
+                               uint64_t nobj, uint64_t nparts, uint64_t seed0, const void* seeds, uint32_t tile,
+                               uint32_t nthreads, void* run, uint64_t* end) {
+    if (!nobj || !nparts) return 0;
+    if (!crc || !len || !run || !nthreads || (!obj_start && nobj != 1))
+        return fail(-EINVAL, "null argument or no threads");
+    if (!scan_tile_ok(tile) || nparts > kScanMaxParts) return fail(-EINVAL, "bad tile or too many parts");
+    std::vector<uint64_t> work(scan_work_words(nparts, tile), 0xA5A5A5A5A5A5A5A5ull);
+    if (crc64) {
+        const ScanIn<uint64_t> in = {static_cast<const uint64_t*>(crc), len, obj_start, nobj, nparts, seed0,
+                                     static_cast<const uint64_t*>(seeds)};
+        scan_replay<Gf64>(in, tile, nthreads, pow_table<Crc64>().x8pow2, work.data(), static_cast<uint64_t*>(run), end);
+    } else {
+        const ScanIn<uint32_t> in = {static_cast<const uint32_t*>(crc), len, obj_start, nobj, nparts, (uint32_t)seed0,
+                                     static_cast<const uint32_t*>(seeds)};
+        scan_replay<Gf32>(in, tile, nthreads, pow_table<Crc32c>().x8pow2, work.data(), static_cast<uint32_t*>(run), end);
+    }
+    return 0;
+}
+
+// tuning.h, bench only: what a caller did before the scan calls existed.
+int photon_crc_util_scan_on_host(int crc64, const void* d_crc, void* h_crc, const uint64_t* h_len,
+                                 const uint64_t* h_obj_start, uint64_t nobj, uint64_t nparts, uint64_t seed,
+                                 void* h_run, void* d_run, void* stream) {
+    if (!d_crc || !h_crc || !h_len || !h_obj_start || !h_run || !d_run) return fail(-EINVAL, "null argument");
+    if (int rc = photon_crc_stream_sync(stream)) return rc;
+    const size_t w = crc64 ? 8 : 4;
+    hipError_t e = hipMemcpy(h_crc, d_crc, nparts * w, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
+    for (uint64_t m = 0; m < nobj; ++m) {
+        if (crc64) {
+            const uint64_t* c = static_cast<const uint64_t*>(h_crc);
+            uint64_t acc = seed;
+            for (uint64_t s = h_obj_start[m]; s < h_obj_start[m + 1]; ++s)
+                static_cast<uint64_t*>(h_run)[s] = acc = crc64ecma_combine(acc, c[s], (uint32_t)h_len[s]);
+        } else {
+            const uint32_t* c = static_cast<const uint32_t*>(h_crc);
+            uint32_t acc = (uint32_t)seed;
+            for (uint64_t s = h_obj_start[m]; s < h_obj_start[m + 1]; ++s)
+                static_cast<uint32_t*>(h_run)[s] = acc = crc32c_combine(acc, c[s], (uint32_t)h_len[s]);
+        }
+    }
+    e = hipMemcpy(d_run, h_run, nparts * w, hipMemcpyHostToDevice);
+    return e == hipSuccess ? 0 : hip_fail(e, "hipMemcpy");
 }
 
 uint64_t photon_crc_verify_work_bytes(uint64_t count) {

@@ -11,6 +11,7 @@
 #include "fold_parts.h"
 #include "gf2.h"
 #include "parts_plan.h"
+#include "scan_parts.h"
 #include "verify_scan.h"
 
 #ifndef PCRC_LANE_SEL
@@ -1845,6 +1846,94 @@ __global__ __launch_bounds__(kVerifyBlock) void verify_stamp_kernel(const T* crc
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += step) {
         void* p = dst_ptr ? dst_ptr[i] : static_cast<void*>(static_cast<char*>(dst) + i * stride);
         if (p) verify_store<T>(p, crc[i]);
+    }
+}
+
+// ------------------------------------------- running CRCs of an object's parts
+// photon_crc32c_scan_parts_n / photon_crc64ecma_scan_parts_n (DESIGN.md
+// §4.11), G = Gf32 / Gf64, P = the power table: the three steps of
+// scan_parts.h. A workgroup of blockDim.x = min(tile, kScanBlock) threads
+// takes a tile, thread t the run fold_run_bounds gives it; the runs' elements
+// (the carry step: the tiles') combine by an inclusive scan through LDS over
+// the threads that have one (scan_active): 16 parts are 4 steps, not 8.
+// Plain loads and stores only; a launch writes the workspace words of its own
+// tiles (reduce, carry) or run[] / end[] of its own tiles (apply), nothing else.
+template <typename G>
+__device__ __forceinline__ ScanElem<typename G::T> scan_block_inclusive(ScanElem<typename G::T> e,
+                                                                        ScanElem<typename G::T>* lds, uint32_t t,
+                                                                        uint32_t nact) {
+    lds[t] = e;
+    __syncthreads();
+    for (uint32_t off = 1; off < nact; off <<= 1) {  // nact: the same on every thread
+        const bool on = t >= off && t < nact;
+        ScanElem<typename G::T> a = e;
+        if (on) a = lds[t - off];
+        __syncthreads();
+        if (on) {
+            e = scan_combine<G>(a, e);
+            lds[t] = e;
+        }
+        __syncthreads();
+    }
+    return e;  // lds[u] = the inclusive element of thread u, for every u < nact
+}
+
+template <typename G, typename P>
+__global__ __launch_bounds__(kScanBlock) void scan_reduce_kernel(ScanIn<typename G::T> in, uint32_t tile,
+                                                                 uint64_t* work, P pt) {
+    typedef typename G::T T;
+    __shared__ ScanElem<T> lds[kScanBlock];
+    const uint64_t tiles = scan_tiles(in.nparts, tile);
+    const uint32_t t = threadIdx.x, nt = blockDim.x;
+    for (uint64_t k = blockIdx.x; k < tiles; k += gridDim.x) {
+        const uint64_t lo = k * tile, hi = scan_tile_end(in.nparts, tile, k);
+        uint64_t a, b;
+        fold_run_bounds(hi - lo, nt, t, &a, &b);
+        const uint32_t nact = scan_active(hi - lo, nt);
+        const ScanElem<T> e = scan_block_inclusive<G>(scan_run<G>(in, lo + a, lo + b, pt.x8pow2), lds, t, nact);
+        if (t == nact - 1u) scan_store<T>(work, tiles, k, e);
+        __syncthreads();
+    }
+}
+
+// One workgroup of kScanChunk threads: a chunk of that many tiles at a time,
+// thread t the tile chunk + t, on top of the carry of the chunks before.
+template <typename G>
+__global__ __launch_bounds__(kScanChunk) void scan_carry_kernel(uint64_t* work, uint64_t tiles) {
+    typedef typename G::T T;
+    __shared__ ScanElem<T> lds[kScanChunk];
+    const uint32_t t = threadIdx.x;
+    ScanElem<T> carry = scan_identity<G>();  // the same on every thread
+    for (uint64_t c0 = 0; c0 < tiles; c0 += kScanChunk) {
+        const uint64_t k = c0 + t;
+        const uint32_t nact = tiles - c0 < kScanChunk ? (uint32_t)(tiles - c0) : kScanChunk;
+        scan_block_inclusive<G>(k < tiles ? scan_load<T>(work, tiles, k) : scan_identity<G>(), lds, t, nact);
+        const ScanElem<T> before = t && t < nact ? lds[t - 1u] : scan_identity<G>();
+        const ScanElem<T> total = lds[nact - 1u];
+        if (k < tiles) scan_store<T>(work, tiles, k, scan_combine<G>(carry, before));
+        carry = scan_combine<G>(carry, total);
+        __syncthreads();
+    }
+}
+
+template <typename G, typename P>
+__global__ __launch_bounds__(kScanBlock) void scan_apply_kernel(ScanIn<typename G::T> in, uint32_t tile,
+                                                                const uint64_t* work, typename G::T* run,
+                                                                uint64_t* end, P pt) {
+    typedef typename G::T T;
+    __shared__ ScanElem<T> lds[kScanBlock];
+    const uint64_t tiles = scan_tiles(in.nparts, tile);
+    const uint32_t t = threadIdx.x, nt = blockDim.x;
+    for (uint64_t k = blockIdx.x; k < tiles; k += gridDim.x) {
+        const uint64_t lo = k * tile, hi = scan_tile_end(in.nparts, tile, k);
+        uint64_t a, b;
+        fold_run_bounds(hi - lo, nt, t, &a, &b);
+        const uint32_t nact = scan_active(hi - lo, nt);
+        scan_block_inclusive<G>(scan_run<G>(in, lo + a, lo + b, pt.x8pow2), lds, t, nact);
+        ScanElem<T> before = tiles > 1 ? scan_load<T>(work, tiles, k) : scan_identity<G>();  // one tile: no workspace
+        if (t && t < nact) before = scan_combine<G>(before, lds[t - 1u]);
+        scan_emit<G>(in, lo + a, lo + b, pt.x8pow2, before, run, end);
+        __syncthreads();
     }
 }
 

@@ -1095,6 +1095,9 @@ __global__ __launch_bounds__(kFoldMaxBlock) void crc64_fold_parts_kernel(const u
     fold_parts_block<Gf64>(crc, len, obj_start, nobj, nparts, seed0, seeds, out, total, pt.x8pow2);
 }
 
+// photon_crc64ecma_scan_parts_n: scan_reduce_kernel / scan_carry_kernel /
+// scan_apply_kernel (crc32c_kernels.h) at Gf64 with this file's PowTable64.
+
 // photon_crc64ecma_copy_parts_n / photon_crc64ecma_batch_parts_n (DESIGN.md
 // §4.9): crc32c_parts_kernel's task space and cut (parts_plan.h, parts_task)
 // with the CRC-64 unit. work[t] = crc64ecma_extend over the piece from seed 0

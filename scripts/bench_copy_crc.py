@@ -91,6 +91,20 @@ the ratio (b)/(a), and the spread between the alternations of each arm;
                     default (photon_crc_set_verify_tile); with the default alone, two more lines
                     give the C2 batch alone against the batch followed by verify_n, by events.
                     --out appends.
+  --scan : running CRCs of objects over their parts (photon_crc32c_scan_parts_n and
+                    photon_crc64ecma_scan_parts_n, both in one run), the same alternations, one JSON
+                    line per CRC and shape (1 object x 16 parts, 1 x 10,000, 1 x 1,048,576, 4,096 x
+                    16; parts of 1 to 16 MiB, the 1 Mi shape uniform 4 KiB): "host" = the route
+                    before the calls existed, natively (photon_crc_util_scan_on_host:
+                    photon_crc_stream_sync, the part CRCs copied to pinned host memory, a serial
+                    chain of the host crc32c_combine / crc64ecma_combine, the running words copied
+                    back), wall clock in us; "device" = the new call, wall clock from the launch to
+                    the stream sync; "device_kernel" = its launches alone by HIP events; for one
+                    object "fold" / "fold_kernel" = fold_parts_n over the same pairs (the last value
+                    only). The arms' values, the fold's and the positions are compared before
+                    anything is timed. At 100,000 parts and more the host and fold arms run a tenth
+                    of --reps ("slow_arm_reps"). --tiles 256,1024,... measures those tiles
+                    (photon_crc_set_scan_tile); --scan-shapes 1x16,... picks shapes. --out appends.
   --parts : copy + CRC of many large parts in one launch
                     (photon_crc32c_copy_parts_n; with --crc64 the CRC-64 call), the same method,
                     device to device, the parts back to back from buf+1 to dbuf+1 (co-aligned):
@@ -135,7 +149,9 @@ ap.add_argument("--sizes", default="64,256,1024", help="--long: payload sizes in
 ap.add_argument("--fold", action="store_true")
 ap.add_argument("--parts", action="store_true")
 ap.add_argument("--verify", action="store_true")
-ap.add_argument("--tiles", default="0", help="--verify: tiles in entries to measure, 0 = the default")
+ap.add_argument("--tiles", default="0", help="--verify, --scan: tiles in entries to measure, 0 = the default")
+ap.add_argument("--scan", action="store_true")
+ap.add_argument("--scan-shapes", help="--scan: objects x parts per object, e.g. 1x16,4096x16 (default: all four)")
 ap.add_argument("--tree", default="working tree", help="--fold: a label of the tree measured, written to each line")
 args = ap.parse_args()
 
@@ -593,6 +609,122 @@ def bench_fold(crc64, nobj, per):
     return res
 
 
+SCAN_SHAPES = [(1, 16), (1, 10000), (1, 1 << 20), (4096, 16)]  # objects x parts per object
+
+
+def bench_scan(crc64, nobj, per, tile):
+    """Running CRCs on the device (scan_parts*_device) against the route before the call existed
+    (photon_crc_util_scan_on_host) and, for one object, against fold_parts*_device of the same pairs, which
+    yields the last value only. Wall time per call with its stream sync, and kernel time by events."""
+    import time
+    rng = np.random.default_rng(0x5CA9 + nobj + per)
+    nparts = nobj * per
+    wdt = np.uint64 if crc64 else np.uint32
+    if per >= 1 << 20:
+        lens = np.full(nparts, 4096, np.uint64)  # a 4 GiB object in 4 KiB blocks
+    else:
+        lens = rng.integers(1 << 20, 1 << 24, nparts).astype(np.uint64)  # unequal parts of 1 to 16 MiB ...
+        lens[per - 1::per] = rng.integers(1, 1 << 20, nobj)              # ... and a short last part
+    crcs = rng.integers(0, 1 << 63, nparts, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    crcs = crcs if crc64 else (crcs >> np.uint64(32)).astype(np.uint32)
+    start = np.arange(nobj + 1, dtype=np.uint64) * np.uint64(per)
+    seed = 0xFEDCBA9876543210 if crc64 else 0x9E3779B1
+    tdt = torch.int64 if crc64 else torch.int32
+    d_crc = torch.from_numpy(crcs.view(np.int64 if crc64 else np.int32)).cuda()
+    d_len = torch.from_numpy(lens.view(np.int64)).cuda()
+    d_start = torch.from_numpy(start.view(np.int64)).cuda()
+    h_crc, h_run = torch.zeros(nparts, dtype=tdt).pin_memory(), torch.zeros(nparts, dtype=tdt).pin_memory()
+    run_a, run_b = torch.zeros(nparts, dtype=tdt, device="cuda"), torch.zeros(nparts, dtype=tdt, device="cuda")
+    end_b = torch.zeros(nparts, dtype=torch.int64, device="cuda")
+    out_f = torch.zeros(nobj, dtype=tdt).pin_memory()
+    ck.set_scan_tile(tile)
+    work = torch.empty(ck.scan_work_bytes(nparts), dtype=torch.uint8, device="cuda")
+    scan = ck.scan_parts64_device if crc64 else ck.scan_parts_device
+    fold = ck.fold_parts64_device if crc64 else ck.fold_parts_device
+    sh = st.cuda_stream
+
+    def host():    # (a): sync, part CRCs to the host, a serial chain of the library's host combine, words back
+        ck._check(lib().photon_crc_util_scan_on_host(int(crc64), d_crc.data_ptr(), h_crc.data_ptr(), lens.ctypes.data,
+                                                     start.ctypes.data, nobj, nparts, seed, h_run.data_ptr(),
+                                                     run_a.data_ptr(), sh))
+
+    def launch():
+        scan(d_crc, d_len, d_start, nobj, nparts, run_b, work, seed=seed, end=end_b, stream=st)
+
+    def device():  # (b): the launches, then the stream sync
+        launch()
+        ck._check(lib().photon_crc_stream_sync(sh))
+
+    def fold_launch():
+        fold(d_crc, d_len, d_start, nobj, nparts, out_f, seed=seed, stream=st)
+
+    def fold_device():  # the parent's call on the same pairs: the last value only
+        fold_launch()
+        ck._check(lib().photon_crc_stream_sync(sh))
+
+    torch.cuda.synchronize()
+    host()
+    device()
+    fold_device()
+    got = run_b.cpu().numpy().view(wdt)
+    assert np.array_equal(run_a.cpu().numpy().view(wdt), got), "the arms' values differ"
+    assert np.array_equal(got[per - 1::per], out_f.numpy().view(wdt)), "the scan's last entries differ from the fold"
+    assert np.array_equal(end_b.cpu().numpy().view(np.uint64).reshape(nobj, per),
+                          np.cumsum(lens.reshape(nobj, per), axis=1))
+    arms = {"host": host, "device": device}
+    kernels = {"device": ("device_kernel", launch)}
+    if nobj == 1:
+        arms["fold"] = fold_device
+        kernels["fold"] = ("fold_kernel", fold_launch)
+    slow = nparts >= 100000  # the host chain and the one-workgroup fold take long here: fewer calls of them
+    times = {k: [] for k in list(arms) + [v[0] for v in kernels.values()]}
+    means = {k: [] for k in times}
+    for r in range(args.rounds):
+        for name in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+            fn = arms[name]
+            few = slow and name != "device"
+            reps, warmup = (max(2, args.reps // 10), 1) if few else (args.reps, args.warmup)
+            for _ in range(warmup):
+                fn()
+            t = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e6)
+            times[name] += t
+            means[name].append(float(np.mean(t)))
+            if name in kernels:  # the kernels alone, by events on the launch stream
+                kname, kfn = kernels[name]
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
+                ev[0].record(st)
+                for k in range(reps):
+                    kfn()
+                    ev[k + 1].record(st)
+                torch.cuda.synchronize()
+                t = [ev[k].elapsed_time(ev[k + 1]) * 1e3 for k in range(reps)]
+                times[kname] += t
+                means[kname].append(float(np.mean(t)))
+    ck.set_scan_tile(0)
+    res = {"shape": "scan", "crc": "crc64ecma" if crc64 else "crc32c", "objects": nobj, "parts_per_object": per,
+           "tile": tile or "default", "tiles": (nparts + (tile or 1024) - 1) // (tile or 1024),
+           "part_bytes": "4096" if per >= 1 << 20 else "1-16 MiB", "tree": args.tree, "rounds": args.rounds,
+           "reps": args.reps, "warmup": args.warmup,
+           "slow_arm_reps": max(2, args.reps // 10) if slow else args.reps}
+    for name in times:
+        us = np.asarray(times[name])
+        res[name] = {"us_mean": round(float(us.mean()), 3), "us_median": round(float(np.median(us)), 3),
+                     "round_means_us": [round(m, 3) for m in means[name]],
+                     "spread_us": round(max(means[name]) - min(means[name]), 3)}
+    a, b = res["host"]["us_mean"], res["device"]["us_mean"]
+    res["ratio_device_over_host"] = round(b / a, 4)
+    res["margin_over_host_spread"] = round((a - b) / max(res["host"]["spread_us"], 1e-9), 2)
+    res["faster_3x"] = bool(a - b > 3 * res["host"]["spread_us"])
+    if nobj == 1:
+        res["ratio_scan_kernel_over_fold_kernel"] = round(res["device_kernel"]["us_mean"] /
+                                                          res["fold_kernel"]["us_mean"], 4)
+    return res
+
+
 VERIFY_ROWS = [(65536, "0"), (65536, "3"), (1 << 20, "0"), (1 << 20, "3"), (1 << 20, "1%")]  # entries, bad ones
 
 
@@ -905,6 +1037,19 @@ if args.verify:
         if args.out:
             with open(args.out, "a") as f:
                 f.write(line + "\n")
+    sys.exit(0)
+
+if args.scan:
+    shapes = [tuple(int(x) for x in sh.split("x")) for sh in args.scan_shapes.split(",")] if args.scan_shapes \
+        else SCAN_SHAPES
+    for tile in args.tiles.split(","):
+        for c64 in (False, True):
+            for nobj, per in shapes:
+                line = json.dumps(bench_scan(c64, nobj, per, int(tile)))
+                print(line, flush=True)
+                if args.out:
+                    with open(args.out, "a") as f:
+                        f.write(line + "\n")
     sys.exit(0)
 
 if args.fold:
