@@ -357,6 +357,65 @@ int photon_crc32c_batch_parts_n(const photon_crc_iovec* d_iov, uint64_t nparts, 
  * of 4 bytes, or 8 if crc64 (~0 when that is more than 2^40 words). */
 uint64_t photon_crc_parts_work_bytes(uint64_t nparts, uint64_t max_part_bytes, int crc64);
 
+/* Copy + CRC-32C of MIXED-SIZE parts: photon_crc32c_copy_parts_n with the
+ * piece tasks PACKED on the device. The calls above give
+ * every part the slots of the longest (nparts x ceil(max_part_bytes / piece)
+ * tasks and workspace words): right for parts of about one length, wrong for
+ * a few thousand buffers from 4 KiB to tens of MiB, or for a cap far above
+ * the real lengths. Here the host passes a bound on the SUM of the lengths
+ * (a pool's size, an object's size, a Content-Length), the piece count of
+ * every part is summed on the device, and the piece kernel runs exactly
+ *     T = sum_i pieces(src_i, n_i)
+ * tasks. The contract of photon_crc32c_copy_parts_n carries over word for
+ * word: n_i = min(d_src[i].len, max_part_bytes) (max_part_bytes may be ~0 at
+ * no cost), [d_dst[i], d_dst[i] + n_i) receives part i, d_out[i] =
+ * crc32c_extend(src_i, n_i, seed_i) bit-identical to that call, the same cut
+ * (pieces anchored at 4 KiB of the source, photon_crc_set_parts_piece),
+ * contract (iv), plain stores only (no atomics, no memset, no per-stream
+ * state), nothing allocated or synchronised, capturable and replayable (the
+ * plan is rebuilt on the device by every replay: the descriptors may change
+ * between replays), concurrent calls with distinct d_out / d_report / d_work,
+ * no CPU fallback. Three things differ:
+ *   - Capacity from the total. A part has at most n_i / piece + 1 pieces
+ *     (its head merges into the first piece; a short last piece needs a
+ *     slot), so for any parts with sum n_i <= max_total_bytes
+ *         T <= C = floor(max_total_bytes / piece) + nparts
+ *     piece slots suffice. d_work holds at least
+ *     photon_crc_parts_packed_work_bytes(nparts, max_total_bytes, crc64)
+ *         = 8 (nparts + 1) + 16 ceil(nparts / 1024) + 8 ceil(C w / 8) + 8 ceil(C / 2)
+ *     bytes of device memory, 8-byte aligned (w = 4, or 8 if crc64): the
+ *     first task of every part and T (nparts + 1 words of 64 bits), two
+ *     64-bit words per plan tile of 1,024 parts, C CRC words, C 32-bit words
+ *     of the task-to-part map. It needs no clearing and holds nothing
+ *     between calls.
+ *   - The report. d_report is four uint64_t of device memory, written by every
+ *     call with nparts > 0: [0] = 1 if T > C, else 0; [1] = T; [2] = sum n_i;
+ *     [3] = C (sums beyond 2^64 saturate at ~0).
+ *   - Overflow writes nothing else. If [0] == 1 (the parts were longer in sum
+ *     than max_total_bytes allowed for), no destination byte and no d_out word
+ *     is written: all or nothing. Looking at [0] before trusting d_out is the
+ *     caller's job, on stream-ordered terms, as with photon_crc_verify_report.
+ *   - nparts == 0 returns 0 and touches nothing, d_report included.
+ *   - -EINVAL before anything is enqueued: a null d_src / d_iov, d_out,
+ *     d_report or d_work, or a null d_dst in the copying forms ("null ...");
+ *     nparts above 2^31; C above 2^40; work_bytes below the size above (both
+ *     numbers in the text); a d_work that is not 8-byte aligned.
+ * Six launches per call (four small plan kernels, the piece kernel, the part
+ * fold). For parts of one length the calls above are the ones to take. */
+int photon_crc32c_copy_parts_packed_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts,
+                                      uint64_t max_part_bytes, uint64_t max_total_bytes, uint32_t seed0,
+                                      const uint32_t* d_seeds, uint32_t* d_out, uint64_t* d_report,
+                                      void* d_work, uint64_t work_bytes, void* stream);
+/* The same without the copy. */
+int photon_crc32c_batch_parts_packed_n(const photon_crc_iovec* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                                       uint64_t max_total_bytes, uint32_t seed0, const uint32_t* d_seeds,
+                                       uint32_t* d_out, uint64_t* d_report, void* d_work,
+                                       uint64_t work_bytes, void* stream);
+/* Bytes of d_work the four _parts_packed_n calls need under the current piece
+ * setting (the formula above); 0 for nparts == 0, ~0 when nparts is above
+ * 2^31 or C above 2^40. */
+uint64_t photon_crc_parts_packed_work_bytes(uint64_t nparts, uint64_t max_total_bytes, int crc64);
+
 /* (many GPUs) ONE logical buffer whose bytes lie on several devices of this
  * process: span i = [d_data, d_data + nbytes) on `device`, the spans in
  * buffer order. Every span runs photon_crc32c_extend_device (from seed 0) on
@@ -512,6 +571,18 @@ int photon_crc64ecma_copy_parts_n(const photon_crc_iovec* d_src, void* const* d_
 int photon_crc64ecma_batch_parts_n(const photon_crc_iovec* d_iov, uint64_t nparts, uint64_t max_part_bytes,
                                    uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out,
                                    void* d_work, uint64_t work_bytes, void* stream);
+/* photon_crc32c_copy_parts_packed_n / photon_crc32c_batch_parts_packed_n for
+ * CRC-64/ECMA: the same arguments, report, overflow rule and workspace
+ * (photon_crc_parts_packed_work_bytes(..., 1): 8-byte CRC words); d_out[i] =
+ * crc64ecma_extend(src_i, n_i, seed_i). */
+int photon_crc64ecma_copy_parts_packed_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts,
+                                         uint64_t max_part_bytes, uint64_t max_total_bytes, uint64_t seed0,
+                                         const uint64_t* d_seeds, uint64_t* d_out, uint64_t* d_report,
+                                         void* d_work, uint64_t work_bytes, void* stream);
+int photon_crc64ecma_batch_parts_packed_n(const photon_crc_iovec* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                                          uint64_t max_total_bytes, uint64_t seed0, const uint64_t* d_seeds,
+                                          uint64_t* d_out, uint64_t* d_report, void* d_work,
+                                          uint64_t work_bytes, void* stream);
 /* photon_crc32c_extend_spans for CRC-64/ECMA (crc64ecma_combine's identity:
  * the inverted CRC folds the same way). */
 int photon_crc64ecma_extend_spans(const photon_crc_span* spans, int nspans, uint64_t seed, uint64_t* h_result);

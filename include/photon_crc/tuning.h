@@ -192,6 +192,28 @@ int photon_crc_set_parts_piece(uint64_t bytes);
 int photon_crc_test_parts_plan(uint64_t addr, uint64_t len, uint64_t max_part_bytes, uint64_t piece, uint64_t* out,
                                int cap);
 
+/* The plan of ONE photon_crc32c_copy_parts_packed_n call over nparts parts of
+ * (addr[i], len[i]) (host arrays; no address is dereferenced), replayed on the
+ * CPU by the steps the plan kernels run
+ * (photonlibos_amd/csrc/parts_packed_plan.h) in a workspace of exactly the
+ * call's size that is never cleared: first[0 .. nparts] (first[nparts] = T),
+ * report[0 .. 3] as the call stores it ([3] = C), and for every task t the
+ * piece kernel runs (min(T, C) of them; none when T > C) tasks[3 t .. 3 t + 2]
+ * = (part, piece offset, piece length) as the piece kernel derives them.
+ * piece: 0 = the current setting. Returns 0, or -EINVAL (null or bad
+ * arguments, nparts == 0 or above 2^31, C above 2^40, task_cap below the
+ * tasks to write). */
+int photon_crc_test_parts_packed_plan(const uint64_t* addr, const uint64_t* len, uint64_t nparts,
+                                      uint64_t max_part_bytes, uint64_t max_total_bytes, uint64_t piece,
+                                      uint64_t* first, uint64_t* report, uint64_t* tasks, uint64_t task_cap);
+
+/* Bench utility (scripts/bench_copy_crc.py --parts-packed): the four PLAN
+ * launches of a photon_crc32c_copy_parts_packed_n /
+ * photon_crc64ecma_copy_parts_packed_n call alone (count, scan, first, owner)
+ * on `stream`, into the report and the workspace of such a call. */
+int photon_crc_util_parts_packed_plan(int crc64, const void* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                                      uint64_t max_total_bytes, uint64_t* d_report, void* d_work, void* stream);
+
 /* Bench utility (scripts/bench_copy_crc.py --parts): the SECOND launch of a
  * photon_crc32c_copy_parts_n / photon_crc64ecma_copy_parts_n call alone -- the
  * part fold kernel over the workspace d_work that such a call with the same

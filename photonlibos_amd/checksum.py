@@ -35,6 +35,8 @@ __all__ = [
     "copy_extend_device", "copy_extend64_device",
     "copy_parts_device", "copy_parts64_device", "batch_parts_device", "batch_parts64_device", "parts_work_bytes",
     "set_parts_piece",
+    "copy_parts_packed_device", "copy_parts64_packed_device", "batch_parts_packed_device",
+    "batch_parts64_packed_device", "parts_packed_work_bytes",
     "series64_device", "combine_series64_device", "fold_parts_device", "fold_parts64_device",
     "crc64ecma_series_at", "crc64ecma_combine_series_at",
     "scan_work_bytes", "set_scan_tile", "scan_parts_device", "scan_parts64_device",
@@ -571,6 +573,51 @@ def batch_parts64_device(iov, nparts, max_part_bytes, out, work, work_bytes=None
     _check(lib().photon_crc64ecma_batch_parts_n(_ptr(iov), nparts, max_part_bytes, seed & 0xFFFFFFFFFFFFFFFF,
                                                 _ptr(seeds), _ptr(out), _ptr(work), _work_bytes(work, work_bytes),
                                                 _stream(stream)))
+
+
+def parts_packed_work_bytes(nparts, max_total_bytes, crc64=False):
+    """Bytes of workspace copy_parts*_packed_device / batch_parts*_packed_device need for nparts parts of at
+    most max_total_bytes bytes in all under the current piece setting (set_parts_piece)."""
+    return lib().photon_crc_parts_packed_work_bytes(nparts, max_total_bytes, int(bool(crc64)))
+
+
+def copy_parts_packed_device(src_iov, dst_ptrs, nparts, max_part_bytes, max_total_bytes, out, report, work,
+                             work_bytes=None, seed=0, seeds=None, stream=None):
+    """copy_parts_device for parts of mixed sizes: the piece tasks are packed on the device, so the work and
+    the workspace follow the SUM of the lengths (max_total_bytes, the host's bound on it) and max_part_bytes
+    may be ~0. report: 4 uint64 on the device, {overflow, tasks, bytes, piece slots}; with report[0] == 1
+    (the parts were longer in sum than max_total_bytes allowed for) nothing else was written. work: device
+    workspace of at least parts_packed_work_bytes(nparts, max_total_bytes) bytes. Async, capturable."""
+    _check(lib().photon_crc32c_copy_parts_packed_n(_ptr(src_iov), _ptr(dst_ptrs), nparts, max_part_bytes,
+                                                   max_total_bytes, seed & 0xFFFFFFFF, _ptr(seeds), _ptr(out),
+                                                   _ptr(report), _ptr(work), _work_bytes(work, work_bytes),
+                                                   _stream(stream)))
+
+
+def copy_parts64_packed_device(src_iov, dst_ptrs, nparts, max_part_bytes, max_total_bytes, out, report, work,
+                               work_bytes=None, seed=0, seeds=None, stream=None):
+    """copy_parts_packed_device for CRC-64/ECMA (uint64 seeds / out; parts_packed_work_bytes(..., crc64=True))."""
+    _check(lib().photon_crc64ecma_copy_parts_packed_n(_ptr(src_iov), _ptr(dst_ptrs), nparts, max_part_bytes,
+                                                      max_total_bytes, seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds),
+                                                      _ptr(out), _ptr(report), _ptr(work),
+                                                      _work_bytes(work, work_bytes), _stream(stream)))
+
+
+def batch_parts_packed_device(iov, nparts, max_part_bytes, max_total_bytes, out, report, work, work_bytes=None,
+                              seed=0, seeds=None, stream=None):
+    """copy_parts_packed_device without the copy. Async, capturable."""
+    _check(lib().photon_crc32c_batch_parts_packed_n(_ptr(iov), nparts, max_part_bytes, max_total_bytes,
+                                                    seed & 0xFFFFFFFF, _ptr(seeds), _ptr(out), _ptr(report),
+                                                    _ptr(work), _work_bytes(work, work_bytes), _stream(stream)))
+
+
+def batch_parts64_packed_device(iov, nparts, max_part_bytes, max_total_bytes, out, report, work, work_bytes=None,
+                                seed=0, seeds=None, stream=None):
+    """batch_parts_packed_device for CRC-64/ECMA (uint64 seeds / out)."""
+    _check(lib().photon_crc64ecma_batch_parts_packed_n(_ptr(iov), nparts, max_part_bytes, max_total_bytes,
+                                                       seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(out),
+                                                       _ptr(report), _ptr(work), _work_bytes(work, work_bytes),
+                                                       _stream(stream)))
 
 
 def series64_device(buffer, part_size, n_parts, out, stream=None):

@@ -513,6 +513,11 @@ struct Crc32c : Gf32 {
     static auto parts_kernel() { return &crc32c_parts_kernel<G, default_rows(G), COPY>; }
     static constexpr auto* kPartsFoldKernel = &crc32c_parts_fold_kernel;
     static constexpr const char* kPartsFoldLaunch = "crc32c_parts_fold_kernel launch";
+    typedef PartsPackedArgs PartsPacked;
+    template <int G, bool COPY>
+    static auto parts_packed_kernel() { return &crc32c_parts_packed_kernel<G, default_rows(G), COPY>; }
+    static constexpr auto* kPartsPackedFoldKernel = &crc32c_parts_packed_fold_kernel;
+    static constexpr const char* kPartsPackedFoldLaunch = "crc32c_parts_packed_fold_kernel launch";
     static constexpr auto* kCombineSeriesKernel = &crc32c_combine_series_kernel;
     // combine_series over empty parts: crc32c_combine_series_hw/sw return the
     // first nonzero part CRC (a kernel of its own). true = launched.
@@ -594,6 +599,14 @@ struct Crc64 : Gf64 {
     }
     static constexpr auto* kPartsFoldKernel = &crc64_parts_fold_kernel;
     static constexpr const char* kPartsFoldLaunch = "crc64_parts_fold_kernel launch";
+    typedef PartsPacked64Args PartsPacked;
+    template <int G, bool COPY>
+    static auto parts_packed_kernel() {
+        if constexpr (COPY && !kCopying64) return static_cast<void (*)(PartsPacked64Args, LaneConsts64)>(nullptr);
+        else return &crc64_parts_packed_kernel<G, COPY>;
+    }
+    static constexpr auto* kPartsPackedFoldKernel = &crc64_parts_packed_fold_kernel;
+    static constexpr const char* kPartsPackedFoldLaunch = "crc64_parts_packed_fold_kernel launch";
     static constexpr auto* kCombineSeriesKernel = &crc64_combine_series_kernel;
     // No rule for empty parts: K = x^0 = 1 in crc64_combine_series_kernel.
     static bool combine_series_of_empty(const T*, uint32_t, uint32_t, T*, hipStream_t) { return false; }
@@ -1834,6 +1847,115 @@ int parts_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts, 
     return piece_rc ? piece_rc : rc;
 }
 
+// ------------------------------------------- mixed-size parts, packed tasks
+// The plan of a packed call: the cap, the piece, the piece slots C and the
+// workspace's layout; 0, or what is beyond the kernels' indices (1: nparts, 2: C).
+struct PackedPlan {
+    uint64_t max_bytes, piece, slots;
+    PackedLayout at;
+};
+int packed_plan(uint64_t nparts, uint64_t max_part_bytes, uint64_t max_total_bytes, uint64_t piece, uint64_t word,
+                PackedPlan* pl) {
+    pl->max_bytes = max_part_bytes < kPartsMaxBytes ? max_part_bytes : kPartsMaxBytes;
+    pl->piece = piece;
+    pl->slots = packed_slots(nparts, max_total_bytes, piece);
+    if (nparts > kPackedMaxParts) return 1;
+    if (pl->slots > kPackedMaxSlots) return 2;
+    pl->at = packed_layout(nparts, pl->slots, word);
+    return 0;
+}
+
+uint32_t packed_grid(uint64_t units) { return units < kPackedMaxGrid ? (uint32_t)(units ? units : 1) : kPackedMaxGrid; }
+
+// The four plan launches of a packed call (count, scan, first, owner); launched(what) tells whether the
+// launch before it was enqueued. false: the chain ended.
+template <typename L>
+bool launch_packed_plan(const photon_crc_iovec* d_src, uint64_t nparts, const PackedPlan& pl, uint64_t* tilew,
+                        uint64_t* first, uint32_t* owner, uint64_t* d_report, hipStream_t st, L launched) {
+    const uint64_t tiles = packed_tiles(nparts);
+    const dim3 tgrid(packed_grid(tiles)), block(kPackedBlock);
+    hipLaunchKernelGGL(parts_packed_count_kernel, tgrid, block, 0, st, d_src, nparts, pl.max_bytes, pl.piece, tilew);
+    if (!launched(" parts_packed_count_kernel launch")) return false;
+    hipLaunchKernelGGL(parts_packed_scan_kernel, dim3(1), block, 0, st, tilew, tiles, nparts, pl.slots, first,
+                       d_report);
+    if (!launched(" parts_packed_scan_kernel launch")) return false;
+    hipLaunchKernelGGL(parts_packed_first_kernel, tgrid, block, 0, st, d_src, nparts, pl.max_bytes, pl.piece,
+                       static_cast<const uint64_t*>(tilew), first);
+    if (!launched(" parts_packed_first_kernel launch")) return false;
+    hipLaunchKernelGGL(parts_packed_owner_kernel, dim3(packed_grid((pl.slots + kPackedBlock - 1) / kPackedBlock)),
+                       block, 0, st, static_cast<const uint64_t*>(first), nparts, pl.slots, owner);
+    return launched(" parts_packed_owner_kernel launch");
+}
+
+// photon_crc32c_copy_parts_packed_n / photon_crc32c_batch_parts_packed_n and
+// the CRC-64 forms: the four plan kernels (count, scan, first, owner), the
+// piece kernel over the packed tasks on the batch kernels' grid (sized for C
+// tasks: T is on the device; lane groups by the piece size as in parts_n),
+// then the part fold, all on `stream` inside one heavy-launch mark. A launch
+// that fails ends the chain: the later ones are not enqueued.
+template <typename W, bool COPY>
+int parts_packed_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts, uint64_t max_part_bytes,
+                   uint64_t max_total_bytes, typename W::T seed0, const typename W::T* d_seeds, typename W::T* d_out,
+                   uint64_t* d_report, void* d_work, uint64_t work_bytes, void* stream) {
+    typedef typename W::T T;
+    if (!nparts) return 0;
+    if (!d_src || !d_out || !d_report || !d_work || (COPY && !d_dst))
+        return fail(-EINVAL, COPY ? "null descriptor array, destination array, output, report or workspace"
+                                  : "null descriptor array, output, report or workspace");
+    PackedPlan pl;
+    const int bad = packed_plan(nparts, max_part_bytes, max_total_bytes, parts_piece_now(), sizeof(T), &pl);
+    if (bad == 1)
+        return fail(-EINVAL, "too many parts: " + std::to_string(nparts) + " are more than " +
+                                 std::to_string(kPackedMaxParts));
+    if (bad)
+        return fail(-EINVAL, "too many piece slots: " + std::to_string(nparts) + " parts of " +
+                                 std::to_string(max_total_bytes) + " bytes in all in pieces of " +
+                                 std::to_string(pl.piece) + " need " + std::to_string(pl.slots) +
+                                 ", more than " + std::to_string(kPackedMaxSlots));
+    if (work_bytes < pl.at.bytes)
+        return fail(-EINVAL, "workspace too small: work_bytes " + std::to_string(work_bytes) + ", needed " +
+                                 std::to_string(pl.at.bytes));
+    if ((uintptr_t)d_work & 7u) return fail(-EINVAL, "the workspace is not 8-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* work = static_cast<char*>(d_work);
+    uint64_t* first = reinterpret_cast<uint64_t*>(work + pl.at.first);
+    uint64_t* tilew = reinterpret_cast<uint64_t*>(work + pl.at.tiles);
+    uint32_t* owner = reinterpret_cast<uint32_t*>(work + pl.at.owner);
+    typename W::PartsPacked a{};
+    a.src = d_src;
+    a.dst = d_dst;
+    a.nparts = nparts;
+    a.max_bytes = pl.max_bytes;
+    a.piece = pl.piece;
+    a.slots = pl.slots;
+    a.first = first;
+    a.owner = owner;
+    a.work = reinterpret_cast<T*>(work + pl.at.crc);
+    int chain_rc = 0;
+    auto launched = [&](const char* what) {  // false: the launch before was not enqueued
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) chain_rc = hip_fail(e, W::kKernel, what);
+        return e == hipSuccess;
+    };
+    const int rc = launch_lanes<W>(pl.slots, W::copy_lanes(pl.piece), true, st, W::kPartsPackedFoldLaunch,
+                                   [&](auto G, dim3 grid, const typename W::Lanes& kc) {
+        const auto kernel = W::template parts_packed_kernel<decltype(G)::value, COPY>();
+        if (!kernel) {
+            chain_rc = fail(-ENOTSUP, "the copying CRC-64 kernels are not part of this A/B build");
+            return;
+        }
+        if (!launch_packed_plan(d_src, nparts, pl, tilew, first, owner, d_report, st, launched)) return;
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, a, kc);
+        if (!launched("_parts_packed_kernel launch")) return;
+        const uint64_t wpb = kPartsFoldBlock / 64, blocks = (nparts + wpb - 1) / wpb;
+        hipLaunchKernelGGL(W::kPartsPackedFoldKernel, dim3(blocks < kPartsFoldMaxGrid ? blocks : kPartsFoldMaxGrid),
+                           dim3(kPartsFoldBlock), 0, st, d_src, nparts, pl.max_bytes, pl.piece, pl.slots,
+                           static_cast<const uint64_t*>(first), static_cast<const T*>(a.work), seed0, d_seeds, d_out,
+                           parts_pow_table<W>(pl.piece), pow_table<W>());
+    });
+    return chain_rc ? chain_rc : rc;
+}
+
 }  // namespace
 
 // For the other translation units of the library (internal.h).
@@ -2818,6 +2940,97 @@ int photon_crc_test_parts_plan(uint64_t addr, uint64_t len, uint64_t max_part_by
     out[0] = pl.per_part;
     out[1] = count;
     return k;
+}
+
+int photon_crc32c_copy_parts_packed_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts,
+                                      uint64_t max_part_bytes, uint64_t max_total_bytes, uint32_t seed0,
+                                      const uint32_t* d_seeds, uint32_t* d_out, uint64_t* d_report, void* d_work,
+                                      uint64_t work_bytes, void* stream) {
+    return parts_packed_n<Crc32c, true>(d_src, d_dst, nparts, max_part_bytes, max_total_bytes, seed0, d_seeds, d_out,
+                                        d_report, d_work, work_bytes, stream);
+}
+
+int photon_crc64ecma_copy_parts_packed_n(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t nparts,
+                                         uint64_t max_part_bytes, uint64_t max_total_bytes, uint64_t seed0,
+                                         const uint64_t* d_seeds, uint64_t* d_out, uint64_t* d_report, void* d_work,
+                                         uint64_t work_bytes, void* stream) {
+    return parts_packed_n<Crc64, true>(d_src, d_dst, nparts, max_part_bytes, max_total_bytes, seed0, d_seeds, d_out,
+                                       d_report, d_work, work_bytes, stream);
+}
+
+int photon_crc32c_batch_parts_packed_n(const photon_crc_iovec* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                                       uint64_t max_total_bytes, uint32_t seed0, const uint32_t* d_seeds,
+                                       uint32_t* d_out, uint64_t* d_report, void* d_work, uint64_t work_bytes,
+                                       void* stream) {
+    return parts_packed_n<Crc32c, false>(d_iov, nullptr, nparts, max_part_bytes, max_total_bytes, seed0, d_seeds,
+                                         d_out, d_report, d_work, work_bytes, stream);
+}
+
+int photon_crc64ecma_batch_parts_packed_n(const photon_crc_iovec* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                                          uint64_t max_total_bytes, uint64_t seed0, const uint64_t* d_seeds,
+                                          uint64_t* d_out, uint64_t* d_report, void* d_work, uint64_t work_bytes,
+                                          void* stream) {
+    return parts_packed_n<Crc64, false>(d_iov, nullptr, nparts, max_part_bytes, max_total_bytes, seed0, d_seeds,
+                                        d_out, d_report, d_work, work_bytes, stream);
+}
+
+uint64_t photon_crc_parts_packed_work_bytes(uint64_t nparts, uint64_t max_total_bytes, int crc64) {
+    if (!nparts) return 0;
+    PackedPlan pl;
+    if (packed_plan(nparts, 0, max_total_bytes, parts_piece_now(), crc64 ? 8 : 4, &pl)) return ~0ull;
+    return pl.at.bytes;
+}
+
+int photon_crc_util_parts_packed_plan(int crc64, const void* d_iov, uint64_t nparts, uint64_t max_part_bytes,
+                                      uint64_t max_total_bytes, uint64_t* d_report, void* d_work, void* stream) {
+    if (!nparts) return 0;
+    if (!d_iov || !d_report || !d_work || ((uintptr_t)d_work & 7u)) return fail(-EINVAL, "null or misaligned argument");
+    PackedPlan pl;
+    if (packed_plan(nparts, max_part_bytes, max_total_bytes, parts_piece_now(), crc64 ? 8 : 4, &pl))
+        return fail(-EINVAL, "too many parts or piece slots");
+    int cus = 0;
+    const int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    char* work = static_cast<char*>(d_work);
+    int rc = 0;
+    launch_packed_plan(static_cast<const photon_crc_iovec*>(d_iov), nparts, pl,
+                       reinterpret_cast<uint64_t*>(work + pl.at.tiles), reinterpret_cast<uint64_t*>(work + pl.at.first),
+                       reinterpret_cast<uint32_t*>(work + pl.at.owner), d_report, static_cast<hipStream_t>(stream),
+                       [&](const char* what) {
+                           const hipError_t e = hipGetLastError();
+                           if (e != hipSuccess) rc = hip_fail(e, "parts_packed", what);
+                           return e == hipSuccess;
+                       });
+    return rc;
+}
+
+int photon_crc_test_parts_packed_plan(const uint64_t* addr, const uint64_t* len, uint64_t nparts,
+                                      uint64_t max_part_bytes, uint64_t max_total_bytes, uint64_t piece,
+                                      uint64_t* first, uint64_t* report, uint64_t* tasks, uint64_t task_cap) {
+    if (!addr || !len || !nparts || !first || !report || (!tasks && task_cap) || piece % kPartsAlign ||
+        piece > kPartsMaxPiece)
+        return fail(-EINVAL, "bad packed plan arguments");
+    PackedPlan pl;
+    if (packed_plan(nparts, max_part_bytes, max_total_bytes, piece ? piece : parts_piece_now(), 4, &pl))
+        return fail(-EINVAL, "too many parts or piece slots");
+    // the workspace as a call has it: exactly its size, never cleared
+    std::vector<uint64_t> work((pl.at.bytes + 7) / 8, 0x5A5A5A5A5A5A5A5Aull);
+    uint8_t* w = reinterpret_cast<uint8_t*>(work.data());
+    packed_replay(addr, len, nparts, pl.max_bytes, pl.piece, pl.slots, 4, w, report);
+    const uint64_t* f = reinterpret_cast<const uint64_t*>(w + pl.at.first);
+    const uint32_t* owner = reinterpret_cast<const uint32_t*>(w + pl.at.owner);
+    for (uint64_t i = 0; i <= nparts; ++i) first[i] = f[i];
+    const uint64_t bound = packed_bound(f[nparts], pl.slots);
+    if (bound > task_cap) return fail(-EINVAL, "short output");
+    for (uint64_t t = 0; t < bound; ++t) {  // as parts_packed_task derives it
+        const uint64_t i = packed_owner_clamp(owner[t], nparts);
+        const uint64_t n = len[i] < pl.max_bytes ? len[i] : pl.max_bytes;
+        const PartsPiece pc = packed_piece(addr[i], n, pl.piece, f[i], t);
+        tasks[3 * t] = i;
+        tasks[3 * t + 1] = pc.off;
+        tasks[3 * t + 2] = pc.len;
+    }
+    return 0;
 }
 
 int photon_crc32c_trim_batch(const photon_crc_component* d_all, const photon_crc_component* d_prefix,

@@ -10,6 +10,7 @@
 #include "../../include/photon_crc/crc32c_gpu.h"
 #include "fold_parts.h"
 #include "gf2.h"
+#include "parts_packed_plan.h"
 #include "parts_plan.h"
 #include "scan_parts.h"
 #include "verify_scan.h"
@@ -2041,6 +2042,245 @@ __global__ __launch_bounds__(kPartsFoldBlock) void crc32c_parts_fold_kernel(cons
                                                                             uint32_t seed0, const uint32_t* seeds,
                                                                             uint32_t* out, PowTable kp, PowTable pt) {
     parts_fold_block<Gf32>(src, nparts, max_bytes, piece, per_part, work, seed0, seeds, out, kp.x8pow2, pt.x8pow2);
+}
+
+// ------------------------------------------- mixed-size parts: piece tasks packed on the device
+// photon_crc32c_copy_parts_packed_n / photon_crc32c_batch_parts_packed_n and
+// the CRC-64 forms: the steps of parts_packed_plan.h. The
+// four plan kernels are the same for both CRCs; plain loads and stores only,
+// and a launch writes the workspace words of its own tiles (count, first) or
+// tasks (owner), the scan the tiles' offsets, first[nparts] and the report.
+__device__ __forceinline__ PackedSum packed_wave_sum(PackedSum s) {
+    for (uint32_t d = 32; d; d >>= 1)
+        s = packed_sum(s, PackedSum{wave_shfl_xor(s.tasks, d), wave_shfl_xor(s.bytes, d)});
+    return s;
+}
+
+// The inclusive saturating sum over the wavefront's lanes below and at lane l.
+__device__ __forceinline__ uint64_t packed_wave_inclusive(uint64_t v, uint32_t l) {
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint64_t u = wave_shfl_up(v, d);
+        if (l >= d) v = packed_add(u, v);
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kPackedBlock) void parts_packed_count_kernel(const photon_crc_iovec* src, uint64_t nparts,
+                                                                          uint64_t max_bytes, uint64_t piece,
+                                                                          uint64_t* tilew) {
+    constexpr uint32_t NW = kPackedBlock / 64;
+    __shared__ uint64_t wtasks[NW], wbytes[NW];
+    const uint64_t tiles = packed_tiles(nparts);
+    const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63u;
+    for (uint64_t k = blockIdx.x; k < tiles; k += gridDim.x) {
+        const uint64_t lo = k * kPackedTile + (uint64_t)t * kPackedRun;
+        PackedSum s = {0, 0};
+        for (uint32_t r = 0; r < kPackedRun; ++r) {
+            if (lo + r >= nparts) break;
+            const photon_crc_iovec v = src[lo + r];
+            s = packed_sum(s, packed_part(reinterpret_cast<uint64_t>(v.base), v.len, max_bytes, piece));
+        }
+        s = packed_wave_sum(s);
+        if (l == 0) {
+            wtasks[w] = s.tasks;
+            wbytes[w] = s.bytes;
+        }
+        __syncthreads();
+        if (t == 0) {
+            PackedSum all = {0, 0};
+            for (uint32_t v = 0; v < NW; ++v) all = packed_sum(all, PackedSum{wtasks[v], wbytes[v]});
+            tilew[k] = all.tasks;
+            tilew[tiles + k] = all.bytes;
+        }
+        __syncthreads();
+    }
+}
+
+// One workgroup of kPackedBlock threads: a chunk of that many tiles at a time,
+// thread t the tile chunk + t, on top of the carry of the chunks before
+// (verify_scan_kernel's walk with saturating sums).
+__global__ __launch_bounds__(kPackedBlock) void parts_packed_scan_kernel(uint64_t* tilew, uint64_t tiles,
+                                                                         uint64_t nparts, uint64_t slots,
+                                                                         uint64_t* first, uint64_t* report) {
+    constexpr uint32_t NW = kPackedBlock / 64;
+    __shared__ uint64_t wsum[NW], wbytes[NW];
+    const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63u;
+    uint64_t carry = 0;  // tasks of the chunks before: the same on every thread
+    uint64_t bytes = 0;  // over this thread's tiles
+    for (uint64_t c0 = 0; c0 < tiles; c0 += kPackedBlock) {
+        const uint64_t k = c0 + t;
+        uint64_t n = 0;
+        if (k < tiles) {
+            n = tilew[k];
+            bytes = packed_add(bytes, tilew[tiles + k]);
+        }
+        const uint64_t inc = packed_wave_inclusive(n, l);
+        const uint64_t up = wave_shfl_up(inc, 1);
+        const uint64_t exc = l ? up : 0ull;  // the lanes below
+        if (l == 63) wsum[w] = inc;
+        __syncthreads();
+        uint64_t before = 0, total = 0;
+        for (uint32_t v = 0; v < NW; ++v) {
+            before = packed_add(before, v < w ? wsum[v] : 0ull);
+            total = packed_add(total, wsum[v]);
+        }
+        if (k < tiles) tilew[k] = packed_add(carry, packed_add(before, exc));
+        carry = packed_add(carry, total);
+        __syncthreads();
+    }
+    bytes = packed_wave_sum(PackedSum{0, bytes}).bytes;
+    if (l == 0) wbytes[w] = bytes;
+    __syncthreads();
+    if (t == 0) {
+        PackedSum all = {carry, 0};
+        for (uint32_t v = 0; v < NW; ++v) all.bytes = packed_add(all.bytes, wbytes[v]);
+        packed_report_store(report, all, slots);
+        first[nparts] = all.tasks;
+    }
+}
+
+__global__ __launch_bounds__(kPackedBlock) void parts_packed_first_kernel(const photon_crc_iovec* src, uint64_t nparts,
+                                                                          uint64_t max_bytes, uint64_t piece,
+                                                                          const uint64_t* tilew, uint64_t* first) {
+    constexpr uint32_t NW = kPackedBlock / 64;
+    __shared__ uint64_t wsum[NW];
+    const uint64_t tiles = packed_tiles(nparts);
+    const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63u;
+    for (uint64_t k = blockIdx.x; k < tiles; k += gridDim.x) {
+        const uint64_t lo = k * kPackedTile + (uint64_t)t * kPackedRun;
+        uint64_t c[kPackedRun], sum = 0;
+        for (uint32_t r = 0; r < kPackedRun; ++r) {
+            c[r] = 0;
+            if (lo + r < nparts) {
+                const photon_crc_iovec v = src[lo + r];
+                c[r] = packed_part(reinterpret_cast<uint64_t>(v.base), v.len, max_bytes, piece).tasks;
+            }
+            sum = packed_add(sum, c[r]);
+        }
+        const uint64_t inc = packed_wave_inclusive(sum, l);
+        const uint64_t up = wave_shfl_up(inc, 1);
+        if (l == 63) wsum[w] = inc;
+        __syncthreads();
+        uint64_t at = packed_add(tilew[k], l ? up : 0ull);  // the tile's offset and the lanes below
+        for (uint32_t v = 0; v < NW; ++v) at = packed_add(at, v < w ? wsum[v] : 0ull);
+        for (uint32_t r = 0; r < kPackedRun; ++r) {
+            if (lo + r < nparts) first[lo + r] = at;
+            at = packed_add(at, c[r]);
+        }
+        __syncthreads();
+    }
+}
+
+// owner[t] for the tasks the piece kernel runs. No LDS and few registers: the
+// search's dependent loads hide behind the other wavefronts of the CU.
+__global__ __launch_bounds__(kPackedBlock) void parts_packed_owner_kernel(const uint64_t* first, uint64_t nparts,
+                                                                          uint64_t slots, uint32_t* owner) {
+    const uint64_t bound = packed_bound(first[nparts], slots);  // <= slots: owner[] has that many words
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < bound; t += step)
+        owner[t] = (uint32_t)packed_owner(first, nparts, t);
+}
+
+// The piece kernel: crc32c_parts_kernel's loop and unit over the packed task
+// space. Task t < min(T, C) is piece t - first[i] of part i = owner[t];
+// work[t] receives its CRC from seed 0.
+template <typename T>
+struct PartsPackedArgsT {
+    const photon_crc_iovec* src;
+    void* const* dst;          // COPY only
+    uint64_t nparts;
+    uint64_t max_bytes;        // the cap on every part's length
+    uint64_t piece;
+    uint64_t slots;            // C: the words of owner[] and work[]
+    const uint64_t* first;     // nparts + 1 words
+    const uint32_t* owner;
+    T* work;
+};
+typedef PartsPackedArgsT<uint32_t> PartsPackedArgs;
+
+// Task t of the packed space (ntasks <= a.slots): the piece's source, length and (COPY) destination.
+template <bool COPY, typename A>
+__device__ __forceinline__ bool parts_packed_task(const A& a, uint64_t ntasks, uint64_t t, const uint8_t** p,
+                                                  uint64_t* n, uint8_t** d) {
+    *p = nullptr;
+    *n = 0;
+    *d = nullptr;
+    if (t >= ntasks) return false;
+    const uint64_t i = packed_owner_clamp(a.owner[t], a.nparts);
+    const uint64_t f = a.first[i];
+    const photon_crc_iovec v = a.src[i];
+    const uint64_t len = v.len < a.max_bytes ? v.len : a.max_bytes;
+    const PartsPiece pc = packed_piece(reinterpret_cast<uint64_t>(v.base), len, a.piece, f, t);
+    if (!pc.len) return false;
+    *p = static_cast<const uint8_t*>(v.base) + pc.off;
+    *n = pc.len;
+    if constexpr (COPY) *d = static_cast<uint8_t*>(a.dst[i]) + pc.off;
+    return true;
+}
+
+template <int G, int U, bool COPY>
+__global__ __launch_bounds__(kBlock) void crc32c_parts_packed_kernel(PartsPackedArgs a, LaneConsts kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
+    constexpr bool kLead = PCRC_BATCH_LEAD || (U == 2 && PCRC_BATCH_LEAD2);  // as crc32c_batch_kernel
+    load_tables<G>(lds, kc);
+
+    constexpr int GPW = 64 / G;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    const LaneAddr la = lane_addr(lane);
+
+    const uint64_t ntasks = packed_bound(a.first[a.nparts], a.slots);  // read once; the same on every lane
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave_id(); wv * GPW < ntasks; wv += nwaves) {
+        const uint64_t t = wv * GPW + grp;
+        const uint8_t* p;
+        uint64_t n;
+        uint8_t* d;
+        const bool active = parts_packed_task<COPY>(a, ntasks, t, &p, &n, &d);
+        if (!__builtin_amdgcn_ballot_w64(active)) continue;  // wave-uniform
+        CopyTo ct;
+        if constexpr (COPY) {
+            if (active) ct = copy_begin<G>(p, d, n, gl);
+        }
+        const uint32_t crc = buffer_crc<G, U, kLead, COPY>(lds, p, n, 0u, gl, la, true, ct);
+        if (active && gl == 0) a.work[t] = crc;
+    }
+}
+
+// The part fold of the packed calls: parts_fold_block with part i's words at
+// work + first[i]. Nothing is stored when the tasks did not fit (T > C); a
+// part whose words would not lie inside work[0 .. C) is passed over (a right
+// plan has none).
+template <typename G>
+__device__ __forceinline__ void parts_packed_fold_block(const photon_crc_iovec* src, uint64_t nparts,
+                                                        uint64_t max_bytes, uint64_t piece, uint64_t slots,
+                                                        const uint64_t* first, const typename G::T* work,
+                                                        typename G::T seed0, const typename G::T* seeds,
+                                                        typename G::T* out, const typename G::T* ktab,
+                                                        const typename G::T* tab) {
+    typedef typename G::T T;
+    if (first[nparts] > slots) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wpb = blockDim.x >> 6;
+    for (uint64_t i = blockIdx.x * wpb + wave_id(); i < nparts; i += gridDim.x * wpb) {
+        const photon_crc_iovec v = src[i];
+        const uint64_t n = v.len < max_bytes ? v.len : max_bytes;
+        const uint64_t base = first[i], count = parts_count(reinterpret_cast<uint64_t>(v.base), n, piece);
+        if (base > slots || count > slots - base) continue;
+        const T seed = seeds ? seeds[i] : seed0;
+        const T x = wave_xor(parts_fold_lane<G>(work + base, reinterpret_cast<uint64_t>(v.base), n, piece, seed, lane,
+                                                ktab, tab));
+        if (lane == 0) out[i] = x;
+    }
+}
+
+__global__ __launch_bounds__(kPartsFoldBlock) void crc32c_parts_packed_fold_kernel(
+    const photon_crc_iovec* src, uint64_t nparts, uint64_t max_bytes, uint64_t piece, uint64_t slots,
+    const uint64_t* first, const uint32_t* work, uint32_t seed0, const uint32_t* seeds, uint32_t* out, PowTable kp,
+    PowTable pt) {
+    parts_packed_fold_block<Gf32>(src, nparts, max_bytes, piece, slots, first, work, seed0, seeds, out, kp.x8pow2,
+                                  pt.x8pow2);
 }
 
 // crc32c_trim (crc.cpp:442-464) per element, including its 32-bit size sum

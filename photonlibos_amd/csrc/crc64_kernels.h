@@ -1141,6 +1141,47 @@ __global__ __launch_bounds__(kPartsFoldBlock) void crc64_parts_fold_kernel(const
     parts_fold_block<Gf64>(src, nparts, max_bytes, piece, per_part, work, seed0, seeds, out, kp.x8pow2, pt.x8pow2);
 }
 
+// photon_crc64ecma_copy_parts_packed_n / photon_crc64ecma_batch_parts_packed_n
+// (DESIGN.md §4.12): crc32c_parts_packed_kernel's task space (parts_packed_plan.h,
+// parts_packed_task) with the CRC-64 unit, an instantiation of its own (TAG 2).
+typedef PartsPackedArgsT<uint64_t> PartsPacked64Args;
+
+template <int G, bool COPY>
+__global__ __launch_bounds__(kBlock) void crc64_parts_packed_kernel(PartsPacked64Args a, LaneConsts64 kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
+    load_tables64<G>(lds, kc);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    constexpr int GPW = 64 / G;
+    const LaneAddr64 la = lane_addr64(lane);
+
+    const uint64_t ntasks = packed_bound(a.first[a.nparts], a.slots);  // read once; the same on every lane
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave_id(); wv * GPW < ntasks; wv += nwaves) {
+        const uint64_t t = wv * GPW + grp;
+        const uint8_t* p;
+        uint64_t n;
+        uint8_t* d;
+        const bool active = parts_packed_task<COPY>(a, ntasks, t, &p, &n, &d);
+        if (!__builtin_amdgcn_ballot_w64(active)) continue;  // wave-uniform
+        CopyTo ct;
+        if constexpr (COPY) {
+            if (active) ct = copy_begin<G>(p, d, n, gl);
+        }
+        const uint64_t reg = buffer_reg64<G, COPY, 2>(lds, p, n, ~0ull, gl, lane, la, true, ct);
+        if (active && gl == 0) a.work[t] = ~reg;
+    }
+}
+
+__global__ __launch_bounds__(kPartsFoldBlock) void crc64_parts_packed_fold_kernel(
+    const photon_crc_iovec* src, uint64_t nparts, uint64_t max_bytes, uint64_t piece, uint64_t slots,
+    const uint64_t* first, const uint64_t* work, uint64_t seed0, const uint64_t* seeds, uint64_t* out, PowTable64 kp,
+    PowTable64 pt) {
+    parts_packed_fold_block<Gf64>(src, nparts, max_bytes, piece, slots, first, work, seed0, seeds, out, kp.x8pow2,
+                                  pt.x8pow2);
+}
+
 // The fold of crc64_copy_iov_seg_kernel's segment CRCs, one
 // WAVEFRONT per message (one thread per message, as crc64_msg_fold_kernel,
 // is a chain of 40 dependent loads and 16 64-step multiplies per thread for

@@ -122,6 +122,19 @@ the ratio (b)/(a), and the spread between the alternations of each arm;
                     between X's alternations; "not_slower_than_hand_built" when parts - hand_built is
                     at most the larger of 3 % of hand_built and three times its spread. --shapes
                     picks shapes by name; --out appends.
+  --parts-packed : copy + CRC of mixed-size parts with the piece tasks packed on the
+                    device (photon_crc32c_copy_parts_packed_n and the CRC-64 call, both in one run),
+                    the same method and layout: 512 parts of seeded lengths of 1 to 16 MiB, 1,024 x
+                    4 MiB, 256 x 16 MiB, and 2,048 parts of seeded log-uniform lengths from 4 KiB to
+                    32 MiB. "packed" = the new call with max_part_bytes = ~0 and max_total_bytes =
+                    the exact sum; "parts" = copy_parts_n with the cap at the longest part;
+                    "parts_cap_1GiB" (ragged shape) = copy_parts_n under a 1 GiB cap; "batch_iov"
+                    (mixed shape) = copy_batch_iov; "plan_only" = the new call's four plan launches
+                    alone (photon_crc_util_parts_packed_plan). "faster_3x_than_parts_cap_1GiB" is true
+                    when parts_cap_1GiB - packed exceeds three times the spread between
+                    parts_cap_1GiB's alternations; "not_slower_than_parts" (uniform shapes) when
+                    packed - parts is at most the larger of 3 % of parts and three times its spread.
+                    --shapes picks shapes by name; --out appends.
 """
 import argparse
 import csv
@@ -148,6 +161,7 @@ ap.add_argument("--long", action="store_true")
 ap.add_argument("--sizes", default="64,256,1024", help="--long: payload sizes in MiB")
 ap.add_argument("--fold", action="store_true")
 ap.add_argument("--parts", action="store_true")
+ap.add_argument("--parts-packed", action="store_true")
 ap.add_argument("--verify", action="store_true")
 ap.add_argument("--tiles", default="0", help="--verify, --scan: tiles in entries to measure, 0 = the default")
 ap.add_argument("--scan", action="store_true")
@@ -1012,6 +1026,114 @@ def bench_parts(shape, what):
             res["empty_tasks_ms"] = round(res["parts_cap_1GiB"]["ms_mean"] - b, 5)
     return res
 
+
+PACKED_SHAPES = ["512xragged", "1024x4MiB", "256x16MiB", "2048xmixed"]
+
+
+def bench_parts_packed(shape, c64):
+    """copy_parts*_packed_device ("packed": max_part_bytes = ~0, max_total_bytes = the exact sum) against the
+    calls that were here before it, in one process: "parts" = copy_parts*_device with the cap at the longest
+    part, "parts_cap_1GiB" (ragged) = the same under a 1 GiB cap, "batch_iov" (mixed) = copy_batch*_iov;
+    "plan_only" = the packed call's four plan launches alone (photon_crc_util_parts_packed_plan)."""
+    if shape == "2048xmixed":  # log-uniform from 4 KiB to 32 MiB
+        nparts = 2048
+        u = np.random.default_rng(0x9A31).uniform(np.log(4096.0), np.log(float(32 << 20)), nparts)
+        lens = np.minimum(np.exp(u).astype(np.uint64), np.uint64(32 << 20))
+    else:
+        nparts, mib, _ = PARTS_SHAPES[shape]
+        if mib is None:
+            lens = np.random.default_rng(0x9A27).integers(1 << 20, (16 << 20) + 1, nparts).astype(np.uint64)
+        else:
+            lens = np.full(nparts, mib << 20, np.uint64)
+    total, cap = int(lens.sum()), int(lens.max())
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+    src = torch.empty(total + 4096, dtype=torch.uint8, device="cuda")
+    dst = torch.zeros(total + 4096, dtype=torch.uint8, device="cuda")
+    assert src.data_ptr() % 4096 == 0 and dst.data_ptr() % 4096 == 0
+    ck.fill_splitmix(src, src.numel(), src.numel(), 1, 0x5EED0301)
+    s0 = d0 = 1
+    sp, dp = src.data_ptr() + s0, dst.data_ptr() + d0
+    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).cuda()
+    iov = np.empty((nparts, 2), np.uint64)
+    iov[:, 0] = np.uint64(sp) + offs
+    iov[:, 1] = lens
+    d_iov, d_dst = i64(iov), i64(np.uint64(dp) + offs)
+    dt, wdt = (torch.int64, np.uint64) if c64 else (torch.int32, np.uint32)
+    out = torch.zeros(nparts, dtype=dt, device="cuda")
+    report = torch.zeros(4, dtype=torch.int64, device="cuda")
+    everything = (1 << 64) - 1
+    ck.set_parts_piece(0)
+    big = shape == "512xragged"
+    work = torch.empty(max(ck.parts_work_bytes(nparts, 1 << 30 if big else cap, c64), 8), dtype=torch.uint8,
+                       device="cuda")
+    pwork = torch.empty(ck.parts_packed_work_bytes(nparts, total, c64), dtype=torch.uint8, device="cuda")
+    copy_parts = ck.copy_parts64_device if c64 else ck.copy_parts_device
+    copy_packed = ck.copy_parts64_packed_device if c64 else ck.copy_parts_packed_device
+
+    def parts(max_bytes=cap):
+        copy_parts(d_iov, d_dst, nparts, max_bytes, out, work, work.numel(), stream=st)
+
+    def packed():
+        copy_packed(d_iov, d_dst, nparts, everything, total, out, report, pwork, pwork.numel(), stream=st)
+
+    def plan_only():
+        ck._check(lib().photon_crc_util_parts_packed_plan(int(c64), d_iov.data_ptr(), nparts, everything, total,
+                                                          report.data_ptr(), pwork.data_ptr(), st.cuda_stream))
+    arms = {"parts": parts, "packed": packed}
+    if big:
+        arms["parts_cap_1GiB"] = lambda: parts(1 << 30)
+    if shape == "2048xmixed":
+        arms["batch_iov"] = lambda: (ck.copy_batch64_iov if c64 else ck.copy_batch_iov)(d_iov, d_dst, nparts, out,
+                                                                                        stream=st)
+    crcs = {}
+    for name, fn in arms.items():  # same CRCs, the right bytes landed, before anything is timed
+        dst.zero_()
+        out.fill_(-1)
+        work.fill_(0x5A)
+        pwork.fill_(0x5A)
+        fn()
+        torch.cuda.synchronize()
+        assert torch.equal(dst[d0:d0 + total], src[s0:s0 + total]), f"{name}: destination differs from the source"
+        assert not bool(dst[:d0].any()) and not bool(dst[d0 + total:].any()), f"{name}: wrote outside"
+        crcs[name] = out.cpu().numpy().view(wdt).copy()
+    for name in crcs:
+        assert np.array_equal(crcs["parts"], crcs[name]), f"the CRCs of parts and {name} differ"
+    rep = [int(x) for x in report.cpu().numpy().view(np.uint64)]
+    assert rep[0] == 0 and rep[2] == total and rep[1] <= rep[3], rep
+    arms["plan_only"] = plan_only
+    res = {"shape": "parts_packed", "crc": "crc64ecma" if c64 else "crc32c", "layout": shape, "nparts": nparts,
+           "bytes": total, "longest": cap, "tasks": rep[1], "slots": rep[3], "packed_work_bytes": pwork.numel(),
+           "parts_work_bytes": ck.parts_work_bytes(nparts, cap, c64), "src": "buf+1", "dst": "dbuf+1",
+           "rounds": args.rounds, "reps": args.reps, "warmup": args.warmup}
+    res.update(alternate(arms))
+    gib = total / 2.0**30
+    for name in arms:
+        if name != "plan_only":
+            res[name]["payload_GiBps_mean"] = round(gib / (res[name]["ms_mean"] * 1e-3), 1)
+    e = res["packed"]["ms_mean"]
+    if big:
+        o = res["parts_cap_1GiB"]
+        res["margin_over_parts_cap_1GiB_spread"] = round((o["ms_mean"] - e) / max(o["spread_ms"], 1e-9), 2)
+        res["faster_3x_than_parts_cap_1GiB"] = bool(o["ms_mean"] - e > 3 * o["spread_ms"])
+    b = res["parts"]
+    res["packed_minus_parts_ms"] = round(e - b["ms_mean"], 5)
+    if shape in ("1024x4MiB", "256x16MiB"):
+        res["allowed_over_parts_ms"] = round(max(0.03 * b["ms_mean"], 3 * b["spread_ms"]), 5)
+        res["not_slower_than_parts"] = bool(e - b["ms_mean"] <= res["allowed_over_parts_ms"])
+    return res
+
+
+if args.parts_packed:
+    for shape in PACKED_SHAPES:
+        if args.shapes != "c2,c3" and shape not in args.shapes.split(","):
+            continue
+        for c64 in (False, True):
+            line = json.dumps(bench_parts_packed(shape, c64))
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+    sys.exit(0)
 
 if args.parts:
     plan = [(s, "copy") for s in PARTS_SHAPES] + [("1024x4MiB", "pieces"), ("256x16MiB", "pieces"),
