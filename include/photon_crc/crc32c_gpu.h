@@ -196,7 +196,8 @@ int photon_crc32c_gather_msg_n(const photon_crc_iovec* d_iov, const uint64_t* d_
  * segment): a piece with (dst - src) % 16 == 0 is read once, any other is
  * copied first and checksummed from the cache. No per-segment CRCs here (a
  * piece is in general neither a source nor a destination segment); for one
- * CRC per segment of ONE side see photon_crc32c_copy_msg_iov_seg_n below. */
+ * CRC per segment of ONE side see photon_crc32c_copy_msg_iov_seg_n below, for
+ * the segment CRCs of BOTH sides photon_crc32c_copy_msg_iov_seg2_n. */
 int photon_crc32c_copy_msg_iov_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
                                  const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
                                  uint64_t nmsg, const uint64_t* d_size,
@@ -227,6 +228,32 @@ int photon_crc32c_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uint64
                                      uint32_t seed0, const uint32_t* d_seeds,
                                      int seg_side, uint32_t* d_seg_out,
                                      uint32_t* d_out, uint64_t* d_copied, void* stream);
+
+/* photon_crc32c_copy_msg_iov_n that also returns one CRC per segment of BOTH
+ * sides, from the same read: exactly the sum of the two one-side calls above
+ * (re-blocking between two block-checksummed layouts: the source-side CRCs
+ * check the stored words, photon_crc32c_verify_n, the destination-side CRCs
+ * stamp the new blocks, photon_crc32c_stamp_n). The copy, k_m, d_out[m]
+ * (bit-identical) and d_copied[m] are those of photon_crc32c_copy_msg_iov_n,
+ * and so are the alignment rule and contract (iv). d_src_seg_out (nsrc
+ * entries, indexed like d_src) holds what the PHOTON_CRC_SEG_OF_SRC call
+ * writes to d_seg_out, d_dst_seg_out (ndst entries, indexed like d_dst) what
+ * the PHOTON_CRC_SEG_OF_DST call writes: crc32c_extend from seed 0 over the
+ * bytes of the segment that took part in the copy -- the whole segment where
+ * the copy covered it, the landed prefix for the segment in which the copy
+ * ended, 0 for a zero-length segment and for every segment of which nothing
+ * landed. Every entry of both arrays for all nmsg messages is written (no
+ * pre-clearing), nothing beyond them. While the call runs the two arrays hold
+ * intermediate values; they must not overlap each other or anything else the
+ * call touches. A null d_src_seg_out or d_dst_seg_out gives -EINVAL.
+ * Asynchronous on `stream` (two kernels), nothing is allocated or
+ * synchronised, no workspace; capturable and replayable. */
+int photon_crc32c_copy_msg_iov_seg2_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                      const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                      uint64_t nmsg, const uint64_t* d_size,
+                                      uint32_t seed0, const uint32_t* d_seeds,
+                                      uint32_t* d_src_seg_out, uint32_t* d_dst_seg_out,
+                                      uint32_t* d_out, uint64_t* d_copied, void* stream);
 
 /* d_out[i] = crc32c_combine(d_crc1[i], d_crc2[i], d_len2[i]) with the
  * reference's shortcuts (crc1 == 0 -> crc2, len2 == 0 -> crc1). */
@@ -545,6 +572,14 @@ int photon_crc64ecma_copy_msg_iov_seg_n(const photon_crc_iovec* d_src, const uin
                                         uint64_t seed0, const uint64_t* d_seeds,
                                         int seg_side, uint64_t* d_seg_out,
                                         uint64_t* d_out, uint64_t* d_copied, void* stream);
+/* photon_crc32c_copy_msg_iov_seg2_n for CRC-64/ECMA: the same arguments and
+ * contract; the entries of both arrays are crc64ecma_extend from seed 0. */
+int photon_crc64ecma_copy_msg_iov_seg2_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                         const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                         uint64_t nmsg, const uint64_t* d_size,
+                                         uint64_t seed0, const uint64_t* d_seeds,
+                                         uint64_t* d_src_seg_out, uint64_t* d_dst_seg_out,
+                                         uint64_t* d_out, uint64_t* d_copied, void* stream);
 /* photon_crc32c_extend_device for CRC-64/ECMA (crc64ecma_extend, crc.cpp:
  * 119-122): the same latency path for spans up to 256 KiB (a small kernel of
  * up to 33 workgroups), one launch over the chip above, the same per-stream

@@ -113,6 +113,10 @@ def _declare(L):
        vp, vp, vp)
     fn("photon_crc64ecma_copy_msg_iov_seg_n", ctypes.c_int, vp, vp, u64, vp, vp, u64, u64, vp, u64, vp, ctypes.c_int,
        vp, vp, vp, vp)
+    fn("photon_crc32c_copy_msg_iov_seg2_n", ctypes.c_int, vp, vp, u64, vp, vp, u64, u64, vp, u32, vp, vp, vp, vp, vp,
+       vp)
+    fn("photon_crc64ecma_copy_msg_iov_seg2_n", ctypes.c_int, vp, vp, u64, vp, vp, u64, u64, vp, u64, vp, vp, vp, vp,
+       vp, vp)
     fn("photon_crc32c_copy_extend_device", ctypes.c_int, vp, vp, u64, u32, vp, vp)
     fn("photon_crc64ecma_copy_extend_device", ctypes.c_int, vp, vp, u64, u64, vp, vp)
     fn("photon_crc64ecma_series_device", ctypes.c_int, vp, u32, u32, vp, vp)

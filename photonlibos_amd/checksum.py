@@ -32,6 +32,7 @@ __all__ = [
     "copy_batch64_strided", "copy_batch64_iov", "gather64_msg_n",
     "copy_msg_iov_n", "copy_msg64_iov_n",
     "copy_msg_iov_seg_n", "copy_msg64_iov_seg_n", "SEG_OF_SRC", "SEG_OF_DST",
+    "copy_msg_iov_seg2_n", "copy_msg64_iov_seg2_n",
     "copy_extend_device", "copy_extend64_device",
     "copy_parts_device", "copy_parts64_device", "batch_parts_device", "batch_parts64_device", "parts_work_bytes",
     "set_parts_piece",
@@ -473,6 +474,29 @@ def copy_msg64_iov_seg_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nms
                                                      _ptr(dst_start), ndst, nmsg, _ptr(size),
                                                      seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), seg_side, _ptr(seg_out),
                                                      _ptr(out), _ptr(copied), _stream(stream)))
+
+
+def copy_msg_iov_seg2_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nmsg, src_seg_out, dst_seg_out, out,
+                        size=None, seed=0, seeds=None, copied=None, stream=None):
+    """copy_msg_iov_n that also returns one CRC-32C per segment of BOTH sides
+    from the same read: src_seg_out (nsrc entries) is what copy_msg_iov_seg_n
+    writes for SEG_OF_SRC, dst_seg_out (ndst entries) what it writes for
+    SEG_OF_DST; every entry of both is written. The two arrays must not overlap
+    each other or anything else the call touches. out / copied as
+    copy_msg_iov_n. Async."""
+    _check(lib().photon_crc32c_copy_msg_iov_seg2_n(_ptr(src_iov), _ptr(src_start), nsrc, _ptr(dst_iov),
+                                                   _ptr(dst_start), ndst, nmsg, _ptr(size), seed & 0xFFFFFFFF,
+                                                   _ptr(seeds), _ptr(src_seg_out), _ptr(dst_seg_out), _ptr(out),
+                                                   _ptr(copied), _stream(stream)))
+
+
+def copy_msg64_iov_seg2_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nmsg, src_seg_out, dst_seg_out, out,
+                          size=None, seed=0, seeds=None, copied=None, stream=None):
+    """copy_msg_iov_seg2_n for CRC-64/ECMA (uint64 seeds / seg outs / out). Async."""
+    _check(lib().photon_crc64ecma_copy_msg_iov_seg2_n(_ptr(src_iov), _ptr(src_start), nsrc, _ptr(dst_iov),
+                                                      _ptr(dst_start), ndst, nmsg, _ptr(size),
+                                                      seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(src_seg_out),
+                                                      _ptr(dst_seg_out), _ptr(out), _ptr(copied), _stream(stream)))
 
 
 def extend64_device(data, nbytes, out, seed=0, stream=None):

@@ -13,6 +13,7 @@
 #include "parts_packed_plan.h"
 #include "parts_plan.h"
 #include "scan_parts.h"
+#include "seg_unscan.h"
 #include "verify_scan.h"
 
 #ifndef PCRC_LANE_SEL
@@ -1531,6 +1532,183 @@ __global__ __launch_bounds__(kBlock) void crc32c_copy_iov_seg_kernel(CopyIovSegA
             if (args.copied) args.copied[m] = (args.size ? args.size[m] : ~0ull) - left;
         }
     }
+}
+
+// photon_crc32c_copy_msg_iov_seg2_n / photon_crc64ecma_copy_msg_iov_seg2_n
+// (DESIGN.md §4.13): one CRC per segment of BOTH sides. Two kernels on the
+// stream. The walk kernel is crc32c_copy_iov_kernel's (crc64_copy_iov_kernel's)
+// piece loop with the running CRC -- chained from seed_m through the whole
+// message, never reset -- stored at the entry of every segment a cursor
+// leaves or ends in; seg_unscan_kernel then turns the running values into
+// per-segment CRCs in place (seg_unscan.h), without reading payload.
+template <typename T>
+struct CopyIovSeg2ArgsT {
+    const photon_crc_iovec* src;
+    const uint64_t* src_start;
+    const photon_crc_iovec* dst;
+    const uint64_t* dst_start;
+    uint64_t nmsg;
+    const uint64_t* size;      // optional
+    const T* seeds;            // optional
+    T* src_seg;                // one entry per source descriptor
+    T* dst_seg;                // one entry per destination descriptor
+    T* out;
+    uint64_t* copied;          // optional
+    T seed0;
+};
+typedef CopyIovSeg2ArgsT<uint32_t> CopyIovSeg2Args;
+
+// No SegFold, no PowTable, no multiply: beside crc32c_copy_iov_kernel's loop
+// only the stores. A zero-length segment makes a zero-length piece as there;
+// its entry receives the unchanged running value. The entries behind the
+// segment in which the walk ended are not touched here.
+template <int G, int U>
+__global__ __launch_bounds__(kBlock) void crc32c_copy_iov_seg2_kernel(CopyIovSeg2Args args, LaneConsts kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
+    constexpr bool kMsgLead = PCRC_MSG_LEAD != 0;
+    load_tables<G>(lds, kc);
+
+    constexpr int GPW = 64 / G;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = wave_id();
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    const LaneAddr la = lane_addr(lane);
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave; wv * GPW < args.nmsg; wv += nwaves) {
+        const uint64_t m = wv * GPW + grp;
+        const bool active = m < args.nmsg;
+        uint32_t acc = args.seed0;
+        uint64_t left = 0;
+        IovCursor<true> s, d;
+        s.begin(args.src, 0, 0);
+        d.begin(args.dst, 0, 0);
+        if (active) {
+            left = args.size ? args.size[m] : ~0ull;
+            if (args.seeds) acc = args.seeds[m];
+            s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
+            d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
+        }
+        while (left && s.more() && d.more()) {
+            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
+            n = n < left ? n : left;
+            const CopyTo ct = copy_begin<G>(s.p, const_cast<uint8_t*>(d.p), n, gl);
+            acc = buffer_crc<G, U, kMsgLead, true>(lds, s.p, n, acc, gl, la, true, ct);
+            s.p += n;
+            d.p += n;
+            s.rem -= n;
+            d.rem -= n;
+            left -= n;
+            if (!left) break;
+            if (!s.rem) {  // the running CRC at the end of source segment s.i
+                if (gl == 0) args.src_seg[s.i] = acc;
+                s.next();
+            }
+            if (!d.rem) {
+                if (gl == 0) args.dst_seg[d.i] = acc;
+                d.next();
+            }
+        }
+        // (an inactive group's cursors are empty)
+        if (gl == 0) {
+            // The segment each side's walk ended in (or before its first byte).
+            if (s.more()) args.src_seg[s.i] = acc;
+            if (d.more()) args.dst_seg[d.i] = acc;
+        }
+        if (active && gl == 0) {
+            args.out[m] = acc;
+            if (args.copied) args.copied[m] = (args.size ? args.size[m] : ~0ull) - left;
+        }
+    }
+}
+
+// The un-scan of the walk's running values (seg_unscan.h), one WAVEFRONT per
+// message, the source side and then the destination side: 64 segments per
+// step, one per lane. k_m = min(size_m, sum src, sum dst) comes from the
+// descriptors' lengths (saturating sums; no payload is read); a wave prefix
+// sum gives the bytes in front of every segment, the neighbouring lane gives
+// P[j-1], and the last lane's P is carried to the next step in a register,
+// so the in-place rewrite never reads an entry it has overwritten: every load
+// of a step is issued before the step's stores. The multiplies of different
+// segments are independent: one per lane. Plain loads and stores; every entry
+// of both sides of every message is written, nothing else.
+constexpr int kUnscanBlock = 256;
+
+template <typename T>
+__device__ __forceinline__ T wave_up(T v, uint32_t off) {  // lane - off's value (lanes < off: their own)
+    if constexpr (sizeof(T) == 8)
+        return ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v >> 32), off, 64) << 32) |
+               (uint32_t)__shfl_up((int)(uint32_t)v, off, 64);
+    else
+        return (T)__shfl_up((int)v, off, 64);
+}
+template <typename T>
+__device__ __forceinline__ T wave_last(T v) {  // lane 63's value
+    if constexpr (sizeof(T) == 8)
+        return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) |
+               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
+    else
+        return (T)__builtin_amdgcn_readlane((int)v, 63);
+}
+// Inclusive saturating prefix sum over the wave.
+__device__ __forceinline__ uint64_t wave_scan_sat(uint64_t v, uint32_t lane) {
+#pragma unroll
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+        const uint64_t o = wave_up(v, off);
+        v = lane >= off ? unscan_sat_add(o, v) : v;
+    }
+    return v;
+}
+
+template <typename G, typename P>
+__global__ __launch_bounds__(kUnscanBlock) void seg_unscan_kernel(CopyIovSeg2ArgsT<typename G::T> a, P pt) {
+    typedef typename G::T T;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t m = (uint64_t)blockIdx.x * (kUnscanBlock / 64) + wave_id();
+    if (m >= a.nmsg) return;  // wave-uniform
+    const uint64_t ss0 = a.src_start[m], ss1 = a.src_start[m + 1];
+    const uint64_t ds0 = a.dst_start[m], ds1 = a.dst_start[m + 1];
+    // A step: the lengths of segments [base, base + 64) of a side and their inclusive sums.
+    auto step = [&](const photon_crc_iovec* v, uint64_t base, uint64_t s1, uint64_t* len, uint64_t* incl) {
+        *len = base + lane < s1 ? v[base + lane].len : 0ull;
+        *incl = wave_scan_sat(*len, lane);
+    };
+    // The first step of each side is kept; a side's sum: that step's, then the rest.
+    auto total = [&](const photon_crc_iovec* v, uint64_t s0, uint64_t s1, uint64_t incl0) {
+        uint64_t t = wave_last(incl0);
+        for (uint64_t base = s0 + 64; base < s1; base += 64) {  // wave-uniform
+            uint64_t len, incl;
+            step(v, base, s1, &len, &incl);
+            t = unscan_sat_add(t, wave_last(incl));
+        }
+        return t;
+    };
+    uint64_t slen, sincl, dlen, dincl;
+    step(a.src, ss0, ss1, &slen, &sincl);
+    step(a.dst, ds0, ds1, &dlen, &dincl);
+    const uint64_t k = unscan_copied(a.size ? a.size[m] : ~0ull, total(a.src, ss0, ss1, sincl),
+                                     total(a.dst, ds0, ds1, dincl));
+    const T seed = a.seeds ? a.seeds[m] : a.seed0;
+    auto side = [&](const photon_crc_iovec* v, uint64_t s0, uint64_t s1, uint64_t len, uint64_t incl, T* seg) {
+        uint64_t carry_bytes = 0;
+        T carry_p = seed;
+        for (uint64_t base = s0; base < s1; base += 64) {  // wave-uniform
+            if (base != s0) step(v, base, s1, &len, &incl);
+            const uint64_t j = base + lane;
+            const uint64_t up = wave_up(incl, 1);
+            const uint64_t before = unscan_sat_add(carry_bytes, lane ? up : 0ull);
+            const uint64_t n = unscan_landed(k, before, len);  // 0 behind s1 (len = 0)
+            const T p = j < s1 && unscan_reached(k, before) ? seg[j] : (T)0;
+            const T pu = wave_up(p, 1);
+            const T prev = lane ? pu : carry_p;
+            carry_bytes = unscan_sat_add(carry_bytes, wave_last(incl));
+            carry_p = wave_last(p);
+            if (j < s1) seg[j] = unscan_diff<G>(p, prev, n, pt.x8pow2);
+        }
+    };
+    side(a.src, ss0, ss1, slen, sincl, a.src_seg);
+    side(a.dst, ds0, ds1, dlen, dincl, a.dst_seg);
 }
 
 // Per-message fold of per-segment CRCs: acc = seed; acc = acc*x^(8 len)+crc.

@@ -880,6 +880,76 @@ __global__ __launch_bounds__(kBlock) void crc64_copy_iov_seg_kernel(CopyIovSeg64
     }
 }
 
+// photon_crc64ecma_copy_msg_iov_seg2_n: crc64_copy_iov_kernel's
+// walk with the running CRC (~reg, chained from seed_m, never reset) stored at
+// the entry of every segment a cursor leaves or ends in, on both sides, as
+// crc32c_copy_iov_seg2_kernel does; seg_unscan_kernel<Gf64> follows.
+typedef CopyIovSeg2ArgsT<uint64_t> CopyIovSeg264Args;
+
+template <int G>
+__global__ __launch_bounds__(kBlock) void crc64_copy_iov_seg2_kernel(CopyIovSeg264Args args, LaneConsts64 kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
+    // Descriptor prefetch as crc64_copy_iov_kernel (the 128-VGPR budget).
+    constexpr bool kPrefetchSrc = G == 64 || G <= 8, kPrefetchDst = G == 64;
+    load_tables64<G>(lds, kc);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    constexpr int GPW = 64 / G;
+    const LaneAddr64 la = lane_addr64(lane);
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave_id(); wv * GPW < args.nmsg; wv += nwaves) {
+        const uint64_t m = wv * GPW + grp;
+        const bool active = m < args.nmsg;
+        uint64_t seed = args.seed0, left = 0;
+        IovCursor<kPrefetchSrc> s;
+        IovCursor<kPrefetchDst> d;
+        s.begin(args.src, 0, 0);
+        d.begin(args.dst, 0, 0);
+        if (active) {
+            left = args.size ? args.size[m] : ~0ull;
+            if (args.seeds) seed = args.seeds[m];
+            s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
+            d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
+        }
+        uint64_t reg = ~seed;  // crc.cpp:119-122
+        while (left && s.more() && d.more()) {
+            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
+            n = n < left ? n : left;
+            const uint8_t* sp = s.p;
+            const CopyTo ct = copy_begin<G>(sp, const_cast<uint8_t*>(d.p), n, gl);
+            s.p += n;
+            d.p += n;
+            s.rem -= n;
+            d.rem -= n;
+            left -= n;
+            const uint64_t r = buffer_reg64<G, true>(lds, sp, n, reg, gl, lane, la, true, ct);
+            const uint64_t v = gl == 0 ? r : 0ull;
+            reg = ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+            if (!left) break;
+            if (!s.rem) {  // the running CRC at the end of source segment s.i
+                if (gl == 0) args.src_seg[s.i] = ~reg;
+                s.next();
+            }
+            if (!d.rem) {
+                if (gl == 0) args.dst_seg[d.i] = ~reg;
+                d.next();
+            }
+        }
+        // (an inactive group's cursors are empty)
+        if (gl == 0) {
+            // The segment each side's walk ended in (or before its first byte).
+            if (s.more()) args.src_seg[s.i] = ~reg;
+            if (d.more()) args.dst_seg[d.i] = ~reg;
+        }
+        if (active && gl == 0) {
+            args.out[m] = ~reg;
+            if (args.copied) args.copied[m] = (args.size ? args.size[m] : ~0ull) - left;
+        }
+    }
+}
+
 // ------------------------------------------------ full-row uniform batches
 // Strided batches whose buffers are made of whole steps: base and stride
 // 16-byte aligned, nbytes a multiple of 2 * 16 G U (an even number of U-row

@@ -49,6 +49,17 @@ the ratio (b)/(a), and the spread between the alternations of each arm;
                     through copy_msg_iov_n and through the new call with a CRC per
                     source block. "faster_3x" is true when pair - seg_dst exceeds three
                     times the spread between pair's alternations. --out appends.
+  --iov-seg2 : the segment CRCs of BOTH sides from the copy between iovectors
+                    (photon_crc32c_copy_msg_iov_seg2_n; with --crc64 the CRC-64 call), the same
+                    method over the shape of --iov-seg (8 x 8 KiB source segments into 16 x 4 KiB
+                    blocks per message). "plain" = copy_msg_iov_n alone (the floor); "seg_dst" =
+                    the one-side call, a CRC per destination block; "today" = what a caller did
+                    before: the one-side call, then batch_iov over the 65,536 source segments on
+                    the same stream (3 bytes moved per payload byte); "seg2" = the new call (2
+                    bytes per payload byte). Every arm's message CRCs, both sides' segment CRCs and
+                    the landed bytes are compared before anything is timed. "faster_3x" is true
+                    when today - seg2 exceeds three times the spread between today's alternations.
+                    --out appends.
   --long : copy + CRC of ONE long buffer over the whole device
                     (photon_crc32c_copy_extend_device; with --crc64 the CRC-64 call), the
                     same method, one JSON line per size (--sizes, MiB), source at buf+1,
@@ -157,6 +168,7 @@ ap.add_argument("--pmc-summary")
 ap.add_argument("--crc64", action="store_true")
 ap.add_argument("--iov", action="store_true")
 ap.add_argument("--iov-seg", action="store_true")
+ap.add_argument("--iov-seg2", action="store_true")
 ap.add_argument("--long", action="store_true")
 ap.add_argument("--sizes", default="64,256,1024", help="--long: payload sizes in MiB")
 ap.add_argument("--fold", action="store_true")
@@ -455,6 +467,102 @@ def bench_iov_seg():
     res["ratio_seg_src_over_plain_mirror"] = round(res["seg_src"]["ms_mean"] / res["plain_mirror"]["ms_mean"], 4)
     res["margin_over_pair_spread"] = round((p - b) / max(res["pair"]["spread_ms"], 1e-9), 2)
     res["faster_3x"] = bool(p - b > 3 * res["pair"]["spread_ms"])
+    return res
+
+
+def bench_iov_seg2():
+    nmsg, big, small = 8192, 8192, 4096
+    nbig_m, nsmall_m = 8, 16
+    msg = nbig_m * big
+    nbig, nsmall, total = nmsg * nbig_m, nmsg * nsmall_m, nmsg * msg
+    src = torch.empty(total, dtype=torch.uint8, device="cuda")
+    dst = torch.zeros(total, dtype=torch.uint8, device="cuda")
+    ck.fill_splitmix(src, big, big, nbig, 0x5EED0101)
+    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).cuda()
+    # the shape of --iov-seg: segment s in 8 KiB slot (4099 s) mod nbig, block q in 4 KiB slot (8191 q) mod nsmall
+    slot = (np.arange(nbig, dtype=np.uint64) * np.uint64(4099)) % np.uint64(nbig)
+    bslot = (np.arange(nsmall, dtype=np.uint64) * np.uint64(8191)) % np.uint64(nsmall)
+
+    def iov(buf, slots, n):
+        a = np.empty((slots.size, 2), np.uint64)
+        a[:, 0] = np.uint64(buf.data_ptr()) + slots * np.uint64(n)
+        a[:, 1] = n
+        return i64(a)
+    big_start = i64(np.arange(nmsg + 1, dtype=np.uint64) * np.uint64(nbig_m))
+    small_start = i64(np.arange(nmsg + 1, dtype=np.uint64) * np.uint64(nsmall_m))
+    s_big, d_small = iov(src, slot, big), iov(dst, bslot, small)
+    dt = torch.int64 if args.crc64 else torch.int32
+    out = torch.zeros(nmsg, dtype=dt, device="cuda")
+    sseg = torch.zeros(nbig, dtype=dt, device="cuda")
+    dseg = torch.zeros(nsmall, dtype=dt, device="cuda")
+    copy_iov = ck.copy_msg64_iov_n if args.crc64 else ck.copy_msg_iov_n
+    copy_seg = ck.copy_msg64_iov_seg_n if args.crc64 else ck.copy_msg_iov_seg_n
+    copy_seg2 = ck.copy_msg64_iov_seg2_n if args.crc64 else ck.copy_msg_iov_seg2_n
+    batch_iov = ck.batch64_iov if args.crc64 else ck.batch_iov
+
+    def today():
+        copy_seg(s_big, big_start, nbig, d_small, small_start, nsmall, nmsg, ck.SEG_OF_DST, dseg, out, stream=st)
+        batch_iov(s_big, nbig, sseg, stream=st)
+    arms = {
+        "plain": lambda: copy_iov(s_big, big_start, nbig, d_small, small_start, nsmall, nmsg, out, stream=st),
+        "seg_dst": lambda: copy_seg(s_big, big_start, nbig, d_small, small_start, nsmall, nmsg, ck.SEG_OF_DST, dseg,
+                                    out, stream=st),
+        "today": today,
+        "seg2": lambda: copy_seg2(s_big, big_start, nbig, d_small, small_start, nsmall, nmsg, sseg, dseg, out,
+                                  stream=st),
+    }
+    idx = lambda a: torch.from_numpy(a.astype(np.int64)).cuda()
+    stream_a = src.view(nbig, big)[idx(slot)].reshape(-1)
+    crcs, ssegs, dsegs = {}, {}, {}
+    for name, fn in arms.items():  # same CRCs, the right bytes landed, before anything is timed
+        dst.zero_()
+        out.fill_(-1)
+        sseg.fill_(-1)
+        dseg.fill_(-1)
+        fn()
+        torch.cuda.synchronize()
+        landed = dst.view(nsmall, small)[idx(bslot)].reshape(-1)
+        assert torch.equal(landed, stream_a), f"{name}: destination differs from the source stream"
+        crcs[name] = out.cpu().numpy().copy()
+        ssegs[name] = sseg.cpu().numpy().copy()
+        dsegs[name] = dseg.cpu().numpy().copy()
+    assert all(np.array_equal(crcs["plain"], crcs[k]) for k in arms), "the arms' message CRCs differ"
+    assert np.array_equal(dsegs["seg_dst"], dsegs["seg2"]) and np.array_equal(dsegs["today"], dsegs["seg2"]), \
+        "the destination block CRCs of seg2 differ from the one-side call's"
+    assert np.array_equal(ssegs["today"], ssegs["seg2"]), "the source segment CRCs of seg2 differ from batch_iov's"
+    del stream_a
+    means = {k: [] for k in arms}
+    times = {k: [] for k in arms}
+    for r in range(args.rounds):
+        for name in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+            fn = arms[name]
+            for _ in range(args.warmup):
+                fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.reps + 1)]
+            ev[0].record(st)
+            for k in range(args.reps):
+                fn()
+                ev[k + 1].record(st)
+            torch.cuda.synchronize()
+            t = [ev[k].elapsed_time(ev[k + 1]) for k in range(args.reps)]
+            times[name] += t
+            means[name].append(float(np.mean(t)))
+    gib = total / 2.0**30
+    res = {"shape": "iov_seg2", "crc": "crc64ecma" if args.crc64 else "crc32c", "nmsg": nmsg, "segments": nbig_m,
+           "segment_bytes": big, "blocks": nsmall_m, "block_bytes": small, "rounds": args.rounds, "reps": args.reps,
+           "warmup": args.warmup}
+    for name in arms:
+        ms = np.asarray(times[name])
+        res[name] = {"ms_mean": round(float(ms.mean()), 5), "ms_median": round(float(np.median(ms)), 5),
+                     "payload_GiBps_mean": round(gib / (ms.mean() * 1e-3), 1),
+                     "round_means_ms": [round(m, 5) for m in means[name]],
+                     "spread_ms": round(max(means[name]) - min(means[name]), 5)}
+    a, b, p, b2 = (res[k]["ms_mean"] for k in ("plain", "seg_dst", "today", "seg2"))
+    res["ratio_seg2_over_today"] = round(b2 / p, 4)
+    res["ratio_seg2_over_plain"] = round(b2 / a, 4)
+    res["ratio_seg2_over_seg_dst"] = round(b2 / b, 4)
+    res["margin_over_today_spread"] = round((p - b2) / max(res["today"]["spread_ms"], 1e-9), 2)
+    res["faster_3x"] = bool(p - b2 > 3 * res["today"]["spread_ms"])
     return res
 
 
@@ -1194,8 +1302,8 @@ if args.long:
                 f.write(line + "\n")
     sys.exit(0)
 
-if args.iov or args.iov_seg:
-    line = json.dumps(bench_iov_seg() if args.iov_seg else bench_iov())
+if args.iov or args.iov_seg or args.iov_seg2:
+    line = json.dumps(bench_iov_seg2() if args.iov_seg2 else bench_iov_seg() if args.iov_seg else bench_iov())
     print(line, flush=True)
     if args.out:
         with open(args.out, "a") as f:
