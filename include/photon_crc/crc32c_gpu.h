@@ -839,6 +839,67 @@ int photon_crc_host_unregister(void* ptr);
 int photon_crc32c_file_strided(int fd, uint64_t offset, uint64_t stride, uint64_t nbytes, uint64_t count,
                                uint32_t seed0, uint32_t* h_out);
 
+/* Overwrite + CRC delta: the write of a sub-range into a
+ * block or object that already has a stored CRC, without rereading the block.
+ * Write i has length n_i (nbytes, or d_src[i].len); O_i = the n_i bytes at
+ * its destination (d_dst_base + i*dst_stride, or d_dst[i]) when the call
+ * starts, N_i = its source bytes. After the call the destination holds N_i and
+ *   d_delta[i] = R(O_i xor N_i),
+ * R = the raw CRC from a zero register (CRC-32C: crc32c_extend(., 0); CRC-64:
+ * ~crc64ecma_extend(., ~0)), which is crc(O_i, s) ^ crc(N_i, s) for every
+ * common seed s. n_i == 0 writes nothing and gives 0. Each of the two streams
+ * is read once and the destination is written once when source and
+ * destination are co-aligned ((dst - src) % 16 == 0); other buffers are
+ * correct, with no performance claim, as for the copy calls.
+ * Contract (iv) applies unchanged: sources are HBM, or pinned / registered
+ * host memory; no byte outside [dst, dst + n) is written; null pointers with
+ * a non-zero count give -EINVAL ("null ..." in photon_crc_last_error());
+ * count == 0 returns 0 and touches nothing; asynchronous on `stream`, nothing
+ * allocated or synchronised; plain stores only and no atomics: capturable and
+ * replayable; no CPU fallback. New here, and the caller's duty: two
+ * destination ranges must not overlap, and a source must not overlap a
+ * destination (with overlap the deltas would depend on the order).
+ * photon_crc_set_lanes_per_buffer and photon_crc_set_batch_grid apply as to
+ * the copy calls; the rows knobs do not. */
+int photon_crc32c_overwrite_batch_strided(const void* src_base, uint64_t src_stride, void* d_dst_base,
+                                          uint64_t dst_stride, uint64_t nbytes, uint64_t count, uint32_t* d_delta,
+                                          void* stream);
+int photon_crc32c_overwrite_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t count,
+                                      uint32_t* d_delta, void* stream);
+int photon_crc64ecma_overwrite_batch_strided(const void* src_base, uint64_t src_stride, void* d_dst_base,
+                                             uint64_t dst_stride, uint64_t nbytes, uint64_t count, uint64_t* d_delta,
+                                             void* stream);
+int photon_crc64ecma_overwrite_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t count,
+                                         uint64_t* d_delta, void* stream);
+
+/* Stored CRCs patched by the deltas of overwrites:
+ *   d_crc_out[t] = d_crc_in[t] ^ XOR over the writes i in
+ *                  [d_tgt_start[t], d_tgt_start[t+1]) of d_delta[i] * x^(8 * d_tail[i]),
+ * d_tail[i] = the 64-bit count of bytes of target t (a block, a whole object)
+ * behind the end of write i; a tail of 0 and a tail >= 2^32 are ordinary. A
+ * null d_tgt_start: write i patches word i, and ntgt must equal nwrites. An
+ * empty group copies the word. d_crc_out may be d_crc_in itself and may not
+ * otherwise overlap it. Called once with block tails grouped by block, and
+ * again with object tails as one group per object, behind the overwrite call
+ * on the same stream with no synchronisation in between, it brings the stored
+ * block CRCs and the objects' CRCs up to date; photon_crc32c_verify_n /
+ * _stamp_n take the words from there.
+ * As the fold calls: ntgt == 0 returns 0 and touches nothing; a null d_delta
+ * or d_tail with nwrites > 0, a null d_crc_in or d_crc_out, or a null
+ * d_tgt_start with ntgt != nwrites gives -EINVAL; one launch, no workspace,
+ * plain stores only (every output word is written by the one workgroup that
+ * owns the target, whose threads share the target's writes); capturable and
+ * replayable. d_tgt_start (ntgt + 1 entries) must be non-decreasing from 0 to
+ * nwrites -- the caller's duty; whatever it holds, nothing outside the arrays
+ * is read or written. A target with millions of writes stays correct but is
+ * the work of one workgroup. */
+int photon_crc32c_patch_n(const uint32_t* d_delta, const uint64_t* d_tail, uint64_t nwrites,
+                          const uint64_t* d_tgt_start, uint64_t ntgt, const uint32_t* d_crc_in, uint32_t* d_crc_out,
+                          void* stream);
+int photon_crc64ecma_patch_n(const uint64_t* d_delta, const uint64_t* d_tail, uint64_t nwrites,
+                             const uint64_t* d_tgt_start, uint64_t ntgt, const uint64_t* d_crc_in, uint64_t* d_crc_out,
+                             void* stream);
+
 /* Runtime shim so that Photon code drives the batches without HIP headers
  * (host code stays Photon C++; HIP stays behind this library):
  *   stream_create / _destroy / _sync: a non-blocking stream of the current

@@ -232,6 +232,16 @@ int photon_crc_util_parts_fold(int crc64, const void* d_src, uint64_t nparts, ui
 int photon_crc_test_fold_parts(int crc64, const void* crc, const uint64_t* len, uint64_t count, uint64_t seed,
                                uint32_t nthreads, uint64_t* result, uint64_t* total);
 
+/* CPU replay of the patch kernel (photon_crc32c_patch_n /
+ * photon_crc64ecma_patch_n; photonlibos_amd/csrc/patch_crc.h): the kernel's
+ * per-thread step and XOR, run on the host for workgroups of `nthreads`
+ * threads. Arguments as the device calls', every array host memory; delta,
+ * crc_in and crc_out are uint64_t words if crc64, else uint32_t; crc_out may
+ * be crc_in. Returns 0, or -EINVAL. */
+int photon_crc_test_patch(int crc64, const void* delta, const uint64_t* tail, uint64_t nwrites,
+                          const uint64_t* tgt_start, uint64_t ntgt, const void* crc_in, void* crc_out,
+                          uint32_t nthreads);
+
 /* Bench utility (scripts/bench_copy_crc.py --fold, arm (a)): the route a
  * caller took before photon_crc32c_fold_parts_n / photon_crc64ecma_fold_parts_n
  * existed, natively: photon_crc_stream_sync(stream), the nparts part CRCs at

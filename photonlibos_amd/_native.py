@@ -159,6 +159,13 @@ def _declare(L):
     fn("photon_crc_set_verify_tile", ctypes.c_int, u32)
     fn("photon_crc_test_verify", ctypes.c_int, ctypes.c_int, vp, vp, u64, vp, u64, u32, u64, vp, vp)
     fn("photon_crc_util_verify_on_host", ctypes.c_int, ctypes.c_int, vp, vp, vp, u64, vp, vp, u64, vp)
+    fn("photon_crc32c_overwrite_batch_strided", ctypes.c_int, vp, u64, vp, u64, u64, u64, vp, vp)
+    fn("photon_crc32c_overwrite_batch_iov", ctypes.c_int, vp, vp, u64, vp, vp)
+    fn("photon_crc64ecma_overwrite_batch_strided", ctypes.c_int, vp, u64, vp, u64, u64, u64, vp, vp)
+    fn("photon_crc64ecma_overwrite_batch_iov", ctypes.c_int, vp, vp, u64, vp, vp)
+    fn("photon_crc32c_patch_n", ctypes.c_int, vp, vp, u64, vp, u64, vp, vp, vp)
+    fn("photon_crc64ecma_patch_n", ctypes.c_int, vp, vp, u64, vp, u64, vp, vp, vp)
+    fn("photon_crc_test_patch", ctypes.c_int, ctypes.c_int, vp, vp, u64, vp, u64, vp, vp, u32)
     # include/photon_crc/checked_batch.h
     fn("photon_crc_pinned_allocate", ctypes.c_int, vp, PhotonRange, ctypes.POINTER(vp))
     fn("photon_crc_pinned_deallocate", ctypes.c_int, vp, vp)

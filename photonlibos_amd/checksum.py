@@ -39,6 +39,8 @@ __all__ = [
     "copy_parts_packed_device", "copy_parts64_packed_device", "batch_parts_packed_device",
     "batch_parts64_packed_device", "parts_packed_work_bytes",
     "series64_device", "combine_series64_device", "fold_parts_device", "fold_parts64_device",
+    "overwrite_batch_strided", "overwrite_batch_iov", "overwrite_batch64_strided", "overwrite_batch64_iov",
+    "patch_device", "patch64_device",
     "crc64ecma_series_at", "crc64ecma_combine_series_at",
     "scan_work_bytes", "set_scan_tile", "scan_parts_device", "scan_parts64_device",
     "VerifyReport", "verify_work_bytes", "set_verify_tile",
@@ -670,6 +672,50 @@ def fold_parts64_device(crcs, lens, obj_start, nobj, nparts, out, seed=0, seeds=
     _check(lib().photon_crc64ecma_fold_parts_n(_ptr(crcs), _ptr(lens), _ptr(obj_start), nobj, nparts,
                                                seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(out), _ptr(total),
                                                _stream(stream)))
+
+
+def overwrite_batch_strided(src, src_stride, dst, dst_stride, nbytes, count, delta, stream=None):
+    """Overwrite + CRC-32C delta: dst + i*dst_stride receives the nbytes at src + i*src_stride,
+    and delta[i] (uint32) = crc32c_extend(old xor new, 0) = the XOR of the range's old and new
+    CRC from any common seed; neither range is read a second time. Destinations must not
+    overlap each other or a source. Async, capturable."""
+    _check(lib().photon_crc32c_overwrite_batch_strided(_ptr(src), src_stride, _ptr(dst), dst_stride, nbytes, count,
+                                                       _ptr(delta), _stream(stream)))
+
+
+def overwrite_batch_iov(src_iov, dst_ptrs, count, delta, stream=None):
+    """overwrite_batch_strided over descriptors: dst_ptrs[i] (a device array of pointers)
+    receives src_iov[i].len bytes from src_iov[i].base. Async, capturable."""
+    _check(lib().photon_crc32c_overwrite_batch_iov(_ptr(src_iov), _ptr(dst_ptrs), count, _ptr(delta),
+                                                   _stream(stream)))
+
+
+def overwrite_batch64_strided(src, src_stride, dst, dst_stride, nbytes, count, delta, stream=None):
+    """overwrite_batch_strided for CRC-64/ECMA: delta[i] (uint64) = crc64ecma(old) ^ crc64ecma(new)
+    from any common seed. Async, capturable."""
+    _check(lib().photon_crc64ecma_overwrite_batch_strided(_ptr(src), src_stride, _ptr(dst), dst_stride, nbytes,
+                                                          count, _ptr(delta), _stream(stream)))
+
+
+def overwrite_batch64_iov(src_iov, dst_ptrs, count, delta, stream=None):
+    """overwrite_batch_iov for CRC-64/ECMA (uint64 deltas). Async, capturable."""
+    _check(lib().photon_crc64ecma_overwrite_batch_iov(_ptr(src_iov), _ptr(dst_ptrs), count, _ptr(delta),
+                                                      _stream(stream)))
+
+
+def patch_device(delta, tail, nwrites, tgt_start, ntgt, crc_in, crc_out, stream=None):
+    """Patch stored CRC-32Cs by the deltas of overwrites: crc_out[t] = crc_in[t] ^ XOR over the
+    writes tgt_start[t]..tgt_start[t+1]-1 of delta[i] * x^(8 tail[i]); tail[i] (uint64) = the
+    bytes of target t behind the end of write i. tgt_start None: write i patches word i
+    (ntgt == nwrites). crc_out may be crc_in. Async, capturable."""
+    _check(lib().photon_crc32c_patch_n(_ptr(delta), _ptr(tail), nwrites, _ptr(tgt_start), ntgt, _ptr(crc_in),
+                                       _ptr(crc_out), _stream(stream)))
+
+
+def patch64_device(delta, tail, nwrites, tgt_start, ntgt, crc_in, crc_out, stream=None):
+    """patch_device for CRC-64/ECMA (uint64 delta / crc_in / crc_out). Async, capturable."""
+    _check(lib().photon_crc64ecma_patch_n(_ptr(delta), _ptr(tail), nwrites, _ptr(tgt_start), ntgt, _ptr(crc_in),
+                                          _ptr(crc_out), _stream(stream)))
 
 
 def scan_work_bytes(nparts):

@@ -59,6 +59,7 @@
 #include "../../include/photon_crc/tuning.h"
 #include "crc32c_kernels.h"
 #include "crc64_kernels.h"
+#include "overwrite_kernels.h"
 #include "long_plan.h"
 #include "multi_device.h"
 #include "gf2.h"
@@ -808,6 +809,34 @@ int launch_copy(const CopyBatch64Args& a, uint64_t units, int g, hipStream_t str
             hipLaunchKernelGGL((crc64_gather_kernel<GG>), grid, dim3(kBlock), 0, stream, a, kc);
         else
             hipLaunchKernelGGL((crc64_batch_kernel<GG, true>), grid, dim3(kBlock), 0, stream, a, kc);
+    });
+}
+
+// The overwrite + delta kernels (crc32c_overwrite_kernel<G, U>,
+// crc64_overwrite_kernel<G, U>): one build per lane-group
+// size with overwrite_rows(G) rows per step (the rows knobs do not apply;
+// photon_crc_set_lanes_per_buffer and photon_crc_set_batch_grid do).
+// Two streams in flight cost 8 VGPRs per row where the copy's one costs 4:
+// 2 rows per step at every lane-group size keep every build inside the 128
+// VGPRs of one 1,024-thread workgroup per CU without scratch.
+#ifndef PCRC_OW_ROWS  // A/B builds (the Makefile's EXTRA): 4
+#define PCRC_OW_ROWS 2
+#endif
+constexpr int overwrite_rows(int /*g*/) { return PCRC_OW_ROWS; }
+
+int launch_overwrite(const OverwriteArgs<uint32_t>& a, int g, hipStream_t stream) {
+    return launch_lanes<Crc32c>(a.count, g, true, stream, "crc32c_overwrite_kernel launch",
+                                [&](auto G, dim3 grid, const LaneConsts& kc) {
+        constexpr int GG = decltype(G)::value;
+        hipLaunchKernelGGL((crc32c_overwrite_kernel<GG, overwrite_rows(GG)>), grid, dim3(kBlock), 0, stream, a, kc);
+    });
+}
+
+int launch_overwrite(const OverwriteArgs<uint64_t>& a, int g, hipStream_t stream) {
+    return launch_lanes<Crc64>(a.count, g, true, stream, "crc64_overwrite_kernel launch",
+                               [&](auto G, dim3 grid, const LaneConsts64& kc) {
+        constexpr int GG = decltype(G)::value;
+        hipLaunchKernelGGL((crc64_overwrite_kernel<GG, overwrite_rows(GG)>), grid, dim3(kBlock), 0, stream, a, kc);
     });
 }
 
@@ -1674,6 +1703,60 @@ int fold_parts_n(const typename W::T* d_crc, const uint64_t* d_len, const uint64
                        d_out, d_total, pow_table<W>());
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, "_fold_parts_kernel launch");
+}
+
+// Overwrite + CRC delta (crc32c_gpu.h):
+// photon_crc32c_overwrite_batch_strided / photon_crc64ecma_overwrite_batch_strided.
+// Lanes as the copy calls take them (W::copy_lanes).
+template <typename W>
+int overwrite_batch_strided(const void* src_base, uint64_t src_stride, void* d_dst_base, uint64_t dst_stride,
+                            uint64_t nbytes, uint64_t count, typename W::T* d_delta, void* stream) {
+    if (!count) return 0;
+    if (!d_delta || ((!src_base || !d_dst_base) && nbytes)) return fail(-EINVAL, "null source, destination or delta output");
+    OverwriteArgs<typename W::T> a{};
+    a.base = static_cast<const uint8_t*>(src_base);
+    a.stride = src_stride;
+    a.nbytes = nbytes;
+    a.count = count;
+    a.dst_base = static_cast<uint8_t*>(d_dst_base);
+    a.dst_stride = dst_stride;
+    a.out = d_delta;
+    return launch_overwrite(a, W::copy_lanes(nbytes), static_cast<hipStream_t>(stream));
+}
+
+// photon_crc32c_overwrite_batch_iov / photon_crc64ecma_overwrite_batch_iov.
+template <typename W>
+int overwrite_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t count, typename W::T* d_delta,
+                        void* stream) {
+    if (!count) return 0;
+    if (!d_src || !d_dst || !d_delta) return fail(-EINVAL, "null descriptor array, destination array or delta output");
+    OverwriteArgs<typename W::T> a{};
+    a.iov = d_src;
+    a.count = count;
+    a.dst = d_dst;
+    a.out = d_delta;
+    return launch_overwrite(a, W::copy_lanes(65536), static_cast<hipStream_t>(stream));
+}
+
+// photon_crc32c_patch_n / photon_crc64ecma_patch_n: one launch, the workgroup
+// size by writes per target as the fold picks its own by parts per object.
+template <typename W>
+int patch_n(const typename W::T* d_delta, const uint64_t* d_tail, uint64_t nwrites, const uint64_t* d_tgt_start,
+            uint64_t ntgt, const typename W::T* d_crc_in, typename W::T* d_crc_out, void* stream) {
+    if (!ntgt) return 0;
+    if (!d_crc_in || !d_crc_out) return fail(-EINVAL, "null CRC input or output");
+    if ((!d_delta || !d_tail) && nwrites) return fail(-EINVAL, "null deltas or tails");
+    if (!d_tgt_start && ntgt != nwrites)
+        return fail(-EINVAL, "a null d_tgt_start means write i patches word i: ntgt must equal nwrites");
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint32_t grid = ntgt < kFoldMaxGrid ? (uint32_t)ntgt : kFoldMaxGrid;
+    hipLaunchKernelGGL((patch_kernel<W, typename W::Pow>), dim3(grid), dim3(fold_parts_block_size(ntgt, nwrites)), 0,
+                       static_cast<hipStream_t>(stream), d_delta, d_tail, nwrites, d_tgt_start, ntgt, d_crc_in,
+                       d_crc_out, pow_table<W>());
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, "_patch_kernel launch");
 }
 
 // ------------------------------------- running CRCs of an object's parts
@@ -2760,6 +2843,58 @@ int photon_crc_test_fold_parts(int crc64, const void* crc, const uint64_t* len, 
     else
         *result = fold_replay<Gf32>(static_cast<const uint32_t*>(crc), len, count, (uint32_t)seed, nthreads,
                                     pow_table<Crc32c>().x8pow2, total);
+    return 0;
+}
+
+int photon_crc32c_overwrite_batch_strided(const void* src_base, uint64_t src_stride, void* d_dst_base,
+                                          uint64_t dst_stride, uint64_t nbytes, uint64_t count, uint32_t* d_delta,
+                                          void* stream) {
+    return overwrite_batch_strided<Crc32c>(src_base, src_stride, d_dst_base, dst_stride, nbytes, count, d_delta, stream);
+}
+
+int photon_crc32c_overwrite_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t count,
+                                      uint32_t* d_delta, void* stream) {
+    return overwrite_batch_iov<Crc32c>(d_src, d_dst, count, d_delta, stream);
+}
+
+int photon_crc64ecma_overwrite_batch_strided(const void* src_base, uint64_t src_stride, void* d_dst_base,
+                                             uint64_t dst_stride, uint64_t nbytes, uint64_t count, uint64_t* d_delta,
+                                             void* stream) {
+    return overwrite_batch_strided<Crc64>(src_base, src_stride, d_dst_base, dst_stride, nbytes, count, d_delta, stream);
+}
+
+int photon_crc64ecma_overwrite_batch_iov(const photon_crc_iovec* d_src, void* const* d_dst, uint64_t count,
+                                         uint64_t* d_delta, void* stream) {
+    return overwrite_batch_iov<Crc64>(d_src, d_dst, count, d_delta, stream);
+}
+
+int photon_crc32c_patch_n(const uint32_t* d_delta, const uint64_t* d_tail, uint64_t nwrites,
+                          const uint64_t* d_tgt_start, uint64_t ntgt, const uint32_t* d_crc_in, uint32_t* d_crc_out,
+                          void* stream) {
+    return patch_n<Crc32c>(d_delta, d_tail, nwrites, d_tgt_start, ntgt, d_crc_in, d_crc_out, stream);
+}
+
+int photon_crc64ecma_patch_n(const uint64_t* d_delta, const uint64_t* d_tail, uint64_t nwrites,
+                             const uint64_t* d_tgt_start, uint64_t ntgt, const uint64_t* d_crc_in, uint64_t* d_crc_out,
+                             void* stream) {
+    return patch_n<Crc64>(d_delta, d_tail, nwrites, d_tgt_start, ntgt, d_crc_in, d_crc_out, stream);
+}
+
+// tuning.h: the patch kernel's steps (patch_crc.h) on the host.
+int photon_crc_test_patch(int crc64, const void* delta, const uint64_t* tail, uint64_t nwrites,
+                          const uint64_t* tgt_start, uint64_t ntgt, const void* crc_in, void* crc_out,
+                          uint32_t nthreads) {
+    if (!ntgt) return 0;
+    if (!crc_in || !crc_out || !nthreads || ((!delta || !tail) && nwrites) || (!tgt_start && ntgt != nwrites))
+        return fail(-EINVAL, "null argument, no threads, or a null tgt_start with ntgt != nwrites");
+    if (crc64)
+        patch_replay<Gf64>(static_cast<const uint64_t*>(delta), tail, nwrites, tgt_start, ntgt,
+                           static_cast<const uint64_t*>(crc_in), static_cast<uint64_t*>(crc_out), nthreads,
+                           pow_table<Crc64>().x8pow2);
+    else
+        patch_replay<Gf32>(static_cast<const uint32_t*>(delta), tail, nwrites, tgt_start, ntgt,
+                           static_cast<const uint32_t*>(crc_in), static_cast<uint32_t*>(crc_out), nthreads,
+                           pow_table<Crc32c>().x8pow2);
     return 0;
 }
 
