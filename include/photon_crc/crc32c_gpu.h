@@ -255,6 +255,47 @@ int photon_crc32c_copy_msg_iov_seg2_n(const photon_crc_iovec* d_src, const uint6
                                       uint32_t* d_src_seg_out, uint32_t* d_dst_seg_out,
                                       uint32_t* d_out, uint64_t* d_copied, void* stream);
 
+/* The ranged read from checksummed blocks: every source segment of a message
+ * (the blocks that cover the range) is read in full, exactly once, and
+ * checksummed, and only a window of the source stream lands in the
+ * destination iovector. With L = the sum of message m's source lengths, D =
+ * the sum of its destination lengths (both saturating), skip_m = d_skip ?
+ * d_skip[m] : 0 and size_m = d_size ? d_size[m] : unlimited,
+ *   a = min(skip_m, L),   k = min(size_m, D, L - a)
+ * (no sum of skip_m and size_m is formed), the window is source-stream bytes
+ * [a, a + k): byte a + j goes to byte j of the destination stream for j < k,
+ * and nothing else is written to any destination. Zero-length segments on
+ * either side are skipped (their base may be null).
+ *   - d_src_seg_out[s] (nsrc entries, indexed like d_src) = crc32c_extend
+ *     from seed 0 over the WHOLE segment s, inside the window or not; 0 for a
+ *     zero-length segment. Every entry of all nmsg messages is written (no
+ *     pre-clearing). Compare them with the blocks' stored words by
+ *     photon_crc32c_verify_n.
+ *   - d_out[m] = crc32c_extend over exactly the k window bytes from seed_m
+ *     (d_seeds ? d_seeds[m] : seed0); the seed itself when k == 0.
+ *   - d_copied[m] = k (optional).
+ *   - d_work: device memory of at least photon_crc_window_work_bytes(nmsg) =
+ *     16 * nmsg bytes, 8-byte aligned; it needs no clearing, keeps nothing
+ *     between calls, and its contents afterwards are unspecified. While the
+ *     call runs d_src_seg_out holds intermediate values; neither may overlap
+ *     anything else the call touches.
+ * The alignment rule of photon_crc32c_copy_msg_iov_n holds per window piece:
+ * one with (dst - src) % 16 == 0 is stored from the registers that feed the
+ * CRC, any other is copied first and checksummed from the cache; bytes outside
+ * the window are loaded once and never stored. Contract (iv) otherwise:
+ * nmsg == 0 returns 0 before any check; a null d_src_start, d_dst_start,
+ * d_out, d_src_seg_out or d_work, a null d_src with nsrc > 0 or a null d_dst
+ * with ndst > 0 gives -EINVAL; no CPU fallback. Asynchronous on `stream` (two
+ * kernels), nothing is allocated or synchronised; capturable, and replayable
+ * with descriptors, d_skip and d_size that change between replays. */
+uint64_t photon_crc_window_work_bytes(uint64_t nmsg);
+int photon_crc32c_copy_msg_iov_window_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                        const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                        uint64_t nmsg, const uint64_t* d_skip, const uint64_t* d_size,
+                                        uint32_t seed0, const uint32_t* d_seeds,
+                                        uint32_t* d_src_seg_out, uint32_t* d_out, uint64_t* d_copied,
+                                        void* d_work, void* stream);
+
 /* d_out[i] = crc32c_combine(d_crc1[i], d_crc2[i], d_len2[i]) with the
  * reference's shortcuts (crc1 == 0 -> crc2, len2 == 0 -> crc1). */
 int photon_crc32c_combine_batch(const uint32_t* d_crc1, const uint32_t* d_crc2, const uint32_t* d_len2,
@@ -580,6 +621,15 @@ int photon_crc64ecma_copy_msg_iov_seg2_n(const photon_crc_iovec* d_src, const ui
                                          uint64_t seed0, const uint64_t* d_seeds,
                                          uint64_t* d_src_seg_out, uint64_t* d_dst_seg_out,
                                          uint64_t* d_out, uint64_t* d_copied, void* stream);
+/* photon_crc32c_copy_msg_iov_window_n for CRC-64/ECMA: the same arguments,
+ * window, workspace and contract; d_src_seg_out and d_out are
+ * crc64ecma_extend values (uint64_t seeds and outputs). */
+int photon_crc64ecma_copy_msg_iov_window_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                           const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                           uint64_t nmsg, const uint64_t* d_skip, const uint64_t* d_size,
+                                           uint64_t seed0, const uint64_t* d_seeds,
+                                           uint64_t* d_src_seg_out, uint64_t* d_out, uint64_t* d_copied,
+                                           void* d_work, void* stream);
 /* photon_crc32c_extend_device for CRC-64/ECMA (crc64ecma_extend, crc.cpp:
  * 119-122): the same latency path for spans up to 256 KiB (a small kernel of
  * up to 33 workgroups), one launch over the chip above, the same per-stream

@@ -117,6 +117,11 @@ def _declare(L):
        vp)
     fn("photon_crc64ecma_copy_msg_iov_seg2_n", ctypes.c_int, vp, vp, u64, vp, vp, u64, u64, vp, u64, vp, vp, vp, vp,
        vp, vp)
+    fn("photon_crc_window_work_bytes", u64, u64)
+    fn("photon_crc32c_copy_msg_iov_window_n", ctypes.c_int, vp, vp, u64, vp, vp, u64, u64, vp, vp, u32, vp, vp, vp, vp,
+       vp, vp)
+    fn("photon_crc64ecma_copy_msg_iov_window_n", ctypes.c_int, vp, vp, u64, vp, vp, u64, u64, vp, vp, u64, vp, vp, vp,
+       vp, vp, vp)
     fn("photon_crc32c_copy_extend_device", ctypes.c_int, vp, vp, u64, u32, vp, vp)
     fn("photon_crc64ecma_copy_extend_device", ctypes.c_int, vp, vp, u64, u64, vp, vp)
     fn("photon_crc64ecma_series_device", ctypes.c_int, vp, u32, u32, vp, vp)

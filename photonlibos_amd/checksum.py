@@ -33,6 +33,7 @@ __all__ = [
     "copy_msg_iov_n", "copy_msg64_iov_n",
     "copy_msg_iov_seg_n", "copy_msg64_iov_seg_n", "SEG_OF_SRC", "SEG_OF_DST",
     "copy_msg_iov_seg2_n", "copy_msg64_iov_seg2_n",
+    "copy_msg_iov_window_n", "copy_msg64_iov_window_n", "window_work_bytes",
     "copy_extend_device", "copy_extend64_device",
     "copy_parts_device", "copy_parts64_device", "batch_parts_device", "batch_parts64_device", "parts_work_bytes",
     "set_parts_piece",
@@ -499,6 +500,36 @@ def copy_msg64_iov_seg2_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nm
                                                       _ptr(dst_start), ndst, nmsg, _ptr(size),
                                                       seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(src_seg_out),
                                                       _ptr(dst_seg_out), _ptr(out), _ptr(copied), _stream(stream)))
+
+
+def window_work_bytes(nmsg):
+    """Bytes of device workspace copy_msg_iov_window_n / copy_msg64_iov_window_n need for nmsg messages."""
+    return lib().photon_crc_window_work_bytes(nmsg)
+
+
+def copy_msg_iov_window_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nmsg, src_seg_out, out, work,
+                          skip=None, size=None, seed=0, seeds=None, copied=None, stream=None):
+    """The ranged read from checksummed blocks: every source segment of a
+    message is read in full and checksummed (src_seg_out, nsrc entries: the
+    CRC-32C from seed 0 of each WHOLE segment, to verify against the blocks'
+    stored words), and only the window [a, a + k) of the source stream lands in
+    the destination iovector, a = min(skip[m], L), k = min(size[m], D, L - a).
+    out[m] = the CRC-32C of exactly the window bytes from the message's seed,
+    copied[m] = k. work: device memory of at least window_work_bytes(nmsg)
+    bytes, 8-byte aligned. Async, capturable."""
+    _check(lib().photon_crc32c_copy_msg_iov_window_n(_ptr(src_iov), _ptr(src_start), nsrc, _ptr(dst_iov),
+                                                     _ptr(dst_start), ndst, nmsg, _ptr(skip), _ptr(size),
+                                                     seed & 0xFFFFFFFF, _ptr(seeds), _ptr(src_seg_out), _ptr(out),
+                                                     _ptr(copied), _ptr(work), _stream(stream)))
+
+
+def copy_msg64_iov_window_n(src_iov, src_start, nsrc, dst_iov, dst_start, ndst, nmsg, src_seg_out, out, work,
+                            skip=None, size=None, seed=0, seeds=None, copied=None, stream=None):
+    """copy_msg_iov_window_n for CRC-64/ECMA (uint64 seeds / src_seg_out / out). Async."""
+    _check(lib().photon_crc64ecma_copy_msg_iov_window_n(_ptr(src_iov), _ptr(src_start), nsrc, _ptr(dst_iov),
+                                                        _ptr(dst_start), ndst, nmsg, _ptr(skip), _ptr(size),
+                                                        seed & 0xFFFFFFFFFFFFFFFF, _ptr(seeds), _ptr(src_seg_out),
+                                                        _ptr(out), _ptr(copied), _ptr(work), _stream(stream)))
 
 
 def extend64_device(data, nbytes, out, seed=0, stream=None):

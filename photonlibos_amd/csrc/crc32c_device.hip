@@ -914,6 +914,47 @@ int launch_copy_iov_seg2(const CopyIovSeg264Args& a, int g, hipStream_t stream) 
     return walk_rc ? walk_rc : rc;
 }
 
+// The finish after a windowed walk kernel, as
+// launch_seg_unscan: inside the walk's HeavyLaunch mark, and not after a walk
+// kernel that was not enqueued.
+template <typename W>
+void launch_window_finish(const CopyIovWindowArgsT<typename W::T>& a, const char* walk_what, int* walk_rc,
+                          hipStream_t stream) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        *walk_rc = hip_fail(e, walk_what);
+        return;
+    }
+    hipLaunchKernelGGL((window_finish_kernel<W, typename W::Pow>),
+                       dim3((a.nmsg + kUnscanBlock / 64 - 1) / (kUnscanBlock / 64)), dim3(kUnscanBlock), 0, stream, a,
+                       pow_table<W>());
+}
+
+// crc32c_copy_iov_window_kernel<G, U> and window_finish_kernel<Crc32c>, both
+// on `stream`: the walk's grid as launch_copy_iov.
+int launch_copy_iov_window(const CopyIovWindowArgs& a, int g, hipStream_t stream) {
+    int walk_rc = 0;
+    const int rc = launch_lanes<Crc32c>(a.nmsg, g, true, stream, "window_finish_kernel launch",
+                                        [&](auto G, dim3 grid, const LaneConsts& kc) {
+        constexpr int GG = decltype(G)::value;
+        hipLaunchKernelGGL((crc32c_copy_iov_window_kernel<GG, default_rows(GG)>), grid, dim3(kBlock), 0, stream, a,
+                           kc);
+        launch_window_finish<Crc32c>(a, "crc32c_copy_iov_window_kernel launch", &walk_rc, stream);
+    });
+    return walk_rc ? walk_rc : rc;
+}
+
+// crc64_copy_iov_window_kernel<G> and window_finish_kernel<Crc64>, as above.
+int launch_copy_iov_window(const CopyIovWindow64Args& a, int g, hipStream_t stream) {
+    int walk_rc = 0;
+    const int rc = launch_copying64(a.nmsg, g, stream, "window_finish_kernel launch",
+                                    [&](auto G, dim3 grid, const LaneConsts64& kc) {
+        hipLaunchKernelGGL(crc64_copy_iov_window_kernel<decltype(G)::value>, grid, dim3(kBlock), 0, stream, a, kc);
+        launch_window_finish<Crc64>(a, "crc64_copy_iov_window_kernel launch", &walk_rc, stream);
+    });
+    return walk_rc ? walk_rc : rc;
+}
+
 // Host-memory pipeline (photon_crc32c_host_batch_strided): per device, a copy
 // stream and a compute stream, kNumStage device staging chunks. Chunk i is
 // copied (H2D, 2-D so any host stride packs densely) while chunk i-1 is
@@ -1605,6 +1646,33 @@ int copy_msg_iov_seg2_n(const photon_crc_iovec* d_src, const uint64_t* d_src_sta
     a.copied = d_copied;
     a.seed0 = seed0;
     return launch_copy_iov_seg2(a, choose_lanes(8192), static_cast<hipStream_t>(stream));
+}
+
+// photon_crc32c_copy_msg_iov_window_n / photon_crc64ecma_copy_msg_iov_window_n.
+template <typename W>
+int copy_msg_iov_window_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                          const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst, uint64_t nmsg,
+                          const uint64_t* d_skip, const uint64_t* d_size, typename W::T seed0,
+                          const typename W::T* d_seeds, typename W::T* d_src_seg_out, typename W::T* d_out,
+                          uint64_t* d_copied, void* d_work, void* stream) {
+    if (!nmsg) return 0;
+    if (!d_src_start || !d_dst_start || !d_out || !d_src_seg_out || !d_work || (!d_src && nsrc) || (!d_dst && ndst))
+        return fail(-EINVAL, "null argument");
+    CopyIovWindowArgsT<typename W::T> a{};
+    a.src = d_src;
+    a.src_start = d_src_start;
+    a.dst = d_dst;
+    a.dst_start = d_dst_start;
+    a.nmsg = nmsg;
+    a.skip = d_skip;
+    a.size = d_size;
+    a.seeds = d_seeds;
+    a.src_seg = d_src_seg_out;
+    a.out = d_out;
+    a.copied = d_copied;
+    a.work = static_cast<uint64_t*>(d_work);
+    a.seed0 = seed0;
+    return launch_copy_iov_window(a, choose_lanes(8192), static_cast<hipStream_t>(stream));
 }
 
 // photon_crc32c_combine_batch / photon_crc64ecma_combine_batch.
@@ -2624,6 +2692,17 @@ int photon_crc32c_copy_msg_iov_seg2_n(const photon_crc_iovec* d_src, const uint6
                                        d_seeds, d_src_seg_out, d_dst_seg_out, d_out, d_copied, stream);
 }
 
+uint64_t photon_crc_window_work_bytes(uint64_t nmsg) { return 16 * nmsg; }
+
+int photon_crc32c_copy_msg_iov_window_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                        const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                        uint64_t nmsg, const uint64_t* d_skip, const uint64_t* d_size, uint32_t seed0,
+                                        const uint32_t* d_seeds, uint32_t* d_src_seg_out, uint32_t* d_out,
+                                        uint64_t* d_copied, void* d_work, void* stream) {
+    return copy_msg_iov_window_n<Crc32c>(d_src, d_src_start, nsrc, d_dst, d_dst_start, ndst, nmsg, d_skip, d_size,
+                                         seed0, d_seeds, d_src_seg_out, d_out, d_copied, d_work, stream);
+}
+
 int photon_crc64ecma_batch_strided(const void* d_base, uint64_t stride, uint64_t nbytes, uint64_t count,
                                    uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out, void* stream) {
     return batch_strided<Crc64>(d_base, stride, nbytes, count, seed0, d_seeds, d_out, stream);
@@ -2757,6 +2836,15 @@ int photon_crc64ecma_copy_msg_iov_seg2_n(const photon_crc_iovec* d_src, const ui
                                          uint64_t* d_out, uint64_t* d_copied, void* stream) {
     return copy_msg_iov_seg2_n<Crc64>(d_src, d_src_start, nsrc, d_dst, d_dst_start, ndst, nmsg, d_size, seed0,
                                       d_seeds, d_src_seg_out, d_dst_seg_out, d_out, d_copied, stream);
+}
+
+int photon_crc64ecma_copy_msg_iov_window_n(const photon_crc_iovec* d_src, const uint64_t* d_src_start, uint64_t nsrc,
+                                           const photon_crc_iovec* d_dst, const uint64_t* d_dst_start, uint64_t ndst,
+                                           uint64_t nmsg, const uint64_t* d_skip, const uint64_t* d_size,
+                                           uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_src_seg_out,
+                                           uint64_t* d_out, uint64_t* d_copied, void* d_work, void* stream) {
+    return copy_msg_iov_window_n<Crc64>(d_src, d_src_start, nsrc, d_dst, d_dst_start, ndst, nmsg, d_skip, d_size,
+                                        seed0, d_seeds, d_src_seg_out, d_out, d_copied, d_work, stream);
 }
 
 int photon_crc64ecma_extend_device(const void* d_data, uint64_t nbytes, uint64_t seed, uint64_t* d_out,

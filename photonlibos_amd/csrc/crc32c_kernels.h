@@ -15,6 +15,7 @@
 #include "scan_parts.h"
 #include "seg_unscan.h"
 #include "verify_scan.h"
+#include "window_finish.h"
 
 #ifndef PCRC_LANE_SEL
 #define PCRC_LANE_SEL 1  // per-lane v_perm selectors instead of rotating the word (+0.3 % on C2)
@@ -1709,6 +1710,168 @@ __global__ __launch_bounds__(kUnscanBlock) void seg_unscan_kernel(CopyIovSeg2Arg
     };
     side(a.src, ss0, ss1, slen, sincl, a.src_seg);
     side(a.dst, ds0, ds1, dlen, dincl, a.dst_seg);
+}
+
+// photon_crc32c_copy_msg_iov_window_n / photon_crc64ecma_copy_msg_iov_window_n
+// (DESIGN.md §4.15): every source segment of a message is read in full and
+// checksummed, and only the window [a, a + k) of the source stream lands in
+// the destination iovector. Two kernels on the stream, as seg2: the walk
+// (crc32c_copy_iov_window_kernel, crc64_copy_iov_window_kernel) and
+// window_finish_kernel (window_finish.h), which reads no payload.
+template <typename T>
+struct CopyIovWindowArgsT {
+    const photon_crc_iovec* src;
+    const uint64_t* src_start;
+    const photon_crc_iovec* dst;
+    const uint64_t* dst_start;
+    uint64_t nmsg;
+    const uint64_t* skip;      // optional
+    const uint64_t* size;      // optional
+    const T* seeds;            // optional
+    T* src_seg;                // one entry per source descriptor
+    T* out;
+    uint64_t* copied;          // optional
+    uint64_t* work;            // two words per message: R(a), R(b)
+    T seed0;
+};
+typedef CopyIovWindowArgsT<uint32_t> CopyIovWindowArgs;
+
+// The seg2 walk's single running CRC, chained from seed 0 and never reset,
+// over the WHOLE source stream: the walk ends with the source, not with the
+// copy. Three runs of pieces, each a loop of its own so that the destination
+// cursor and the cap are held only where they are used (in one loop with two
+// counters every CRC-64 build spilled):
+//   in front of the window   n = min(s.rem, bytes to a)     CopyTo{}: no store
+//   inside it                n = min(s.rem, d.rem, left)    copy_begin, as crc32c_copy_iov_kernel
+//   behind it                n = s.rem                      CopyTo{}: no store
+// The first run ends at a = min(skip, L); the running value there goes to
+// work[2m]. The second is crc32c_copy_iov_kernel's loop: the window closes
+// when the cap is used up, the destination is exhausted or the source ends,
+// and the running value there goes to work[2m + 1]. The third reads what is
+// left of the source. Both words are always stored; window_finish_kernel reads
+// them only when k > 0. Every source segment's entry receives the running
+// value at the segment's end, in whichever run its last byte falls (one that
+// ends with the cap: at the start of the third run, by a piece of no bytes).
+// No multiply here.
+template <int G, int U>
+__global__ __launch_bounds__(kBlock) void crc32c_copy_iov_window_kernel(CopyIovWindowArgs args, LaneConsts kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
+    constexpr bool kMsgLead = PCRC_MSG_LEAD != 0;
+    load_tables<G>(lds, kc);
+
+    constexpr int GPW = 64 / G;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = wave_id();
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    const LaneAddr la = lane_addr(lane);
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave; wv * GPW < args.nmsg; wv += nwaves) {
+        const uint64_t m = wv * GPW + grp;
+        const bool active = m < args.nmsg;
+        uint32_t acc = 0;
+        IovCursor<true> s;
+        s.begin(args.src, 0, 0);
+        if (active) s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
+        auto piece = [&](uint64_t n, CopyTo ct) {  // n bytes at the source cursor
+            acc = buffer_crc<G, U, kMsgLead, true>(lds, s.p, n, acc, gl, la, true, ct);
+            s.p += n;
+            s.rem -= n;
+        };
+        auto seg_end = [&] {  // the running CRC at the end of source segment s.i
+            if (!s.rem) {
+                if (gl == 0) args.src_seg[s.i] = acc;
+                s.next();
+            }
+        };
+        auto skim = [&](uint64_t cnt) {  // up to cnt source bytes, none stored
+            while (cnt && s.more()) {
+                const uint64_t n = s.rem < cnt ? s.rem : cnt;
+                cnt -= n;
+                piece(n, CopyTo{});
+                seg_end();
+            }
+        };
+        skim(active && args.skip ? args.skip[m] : 0ull);
+        uint64_t left = 0;
+        IovCursor<true> d;
+        d.begin(args.dst, 0, 0);
+        if (active) {
+            if (gl == 0) args.work[2 * m] = acc;  // R(a)
+            left = args.size ? args.size[m] : ~0ull;
+            d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
+        }
+        while (left && s.more() && d.more()) {
+            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
+            n = n < left ? n : left;
+            const CopyTo ct = copy_begin<G>(s.p, const_cast<uint8_t*>(d.p), n, gl);
+            piece(n, ct);
+            d.p += n;
+            d.rem -= n;
+            left -= n;
+            if (!left) break;
+            seg_end();
+            if (!d.rem) d.next();
+        }
+        if (active && gl == 0) args.work[2 * m + 1] = acc;  // R(b)
+        skim(~0ull);
+    }
+}
+
+// The finish of the windowed walk (window_finish.h), one WAVEFRONT per message
+// as seg_unscan_kernel: L and D from the descriptors' lengths (saturating
+// sums), the bounds a and k, the source entries un-scanned in place (every
+// segment was reached, the seed is 0: k = L in the un-scan's terms), then
+// out[m] and copied[m] by the first lane -- one multiply by x^(8k) beyond the
+// un-scan. Plain loads and stores; no payload is read.
+template <typename G, typename P>
+__global__ __launch_bounds__(kUnscanBlock) void window_finish_kernel(CopyIovWindowArgsT<typename G::T> a, P pt) {
+    typedef typename G::T T;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t m = (uint64_t)blockIdx.x * (kUnscanBlock / 64) + wave_id();
+    if (m >= a.nmsg) return;  // wave-uniform
+    const uint64_t ss0 = a.src_start[m], ss1 = a.src_start[m + 1];
+    const uint64_t ds0 = a.dst_start[m], ds1 = a.dst_start[m + 1];
+    auto step = [&](const photon_crc_iovec* v, uint64_t base, uint64_t s1, uint64_t* len, uint64_t* incl) {
+        *len = base + lane < s1 ? v[base + lane].len : 0ull;
+        *incl = wave_scan_sat(*len, lane);
+    };
+    auto total = [&](const photon_crc_iovec* v, uint64_t s0, uint64_t s1, uint64_t incl0) {
+        uint64_t t = wave_last(incl0);
+        for (uint64_t base = s0 + 64; base < s1; base += 64) {  // wave-uniform
+            uint64_t len, incl;
+            step(v, base, s1, &len, &incl);
+            t = unscan_sat_add(t, wave_last(incl));
+        }
+        return t;
+    };
+    uint64_t len, incl, dlen, dincl;
+    step(a.src, ss0, ss1, &len, &incl);
+    step(a.dst, ds0, ds1, &dlen, &dincl);
+    const uint64_t L = total(a.src, ss0, ss1, incl);
+    const uint64_t D = total(a.dst, ds0, ds1, dincl);
+    const Window w = window_bounds(a.skip ? a.skip[m] : 0ull, a.size ? a.size[m] : ~0ull, L, D);
+    uint64_t carry_bytes = 0;
+    T carry_p = 0;
+    for (uint64_t base = ss0; base < ss1; base += 64) {  // wave-uniform
+        if (base != ss0) step(a.src, base, ss1, &len, &incl);
+        const uint64_t j = base + lane;
+        const uint64_t up = wave_up(incl, 1);
+        const uint64_t before = unscan_sat_add(carry_bytes, lane ? up : 0ull);
+        const uint64_t n = unscan_landed(L, before, len);  // 0 behind ss1 (len = 0)
+        const T p = j < ss1 && unscan_reached(L, before) ? a.src_seg[j] : (T)0;
+        const T pu = wave_up(p, 1);
+        const T prev = lane ? pu : carry_p;
+        carry_bytes = unscan_sat_add(carry_bytes, wave_last(incl));
+        carry_p = wave_last(p);
+        if (j < ss1) a.src_seg[j] = unscan_diff<G>(p, prev, n, pt.x8pow2);
+    }
+    if (lane == 0) {
+        const T seed = a.seeds ? a.seeds[m] : a.seed0;
+        a.out[m] = w.k ? window_crc<G>(seed, (T)a.work[2 * m], (T)a.work[2 * m + 1], w.k, pt.x8pow2) : seed;
+        if (a.copied) a.copied[m] = w.k;
+    }
 }
 
 // Per-message fold of per-segment CRCs: acc = seed; acc = acc*x^(8 len)+crc.

@@ -950,6 +950,95 @@ __global__ __launch_bounds__(kBlock) void crc64_copy_iov_seg2_kernel(CopyIovSeg2
     }
 }
 
+// photon_crc64ecma_copy_msg_iov_window_n: the windowed walk
+// of crc32c_copy_iov_window_kernel (the three runs of pieces and the stores are
+// described there) with the CRC-64 copying unit. The register is chained from
+// ~0 (seed 0) over the whole source stream and stored inverted;
+// window_finish_kernel<Crc64> follows.
+typedef CopyIovWindowArgsT<uint64_t> CopyIovWindow64Args;
+
+template <int G>
+__global__ __launch_bounds__(kBlock) void crc64_copy_iov_window_kernel(CopyIovWindow64Args args, LaneConsts64 kc) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
+    // No descriptor prefetch on either side: the 128-VGPR budget.
+    load_tables64<G>(lds, kc);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gl = lane & (G - 1);
+    const uint32_t grp = lane / G;
+    constexpr int GPW = 64 / G;
+    const LaneAddr64 la = lane_addr64(lane);
+
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave_id(); wv * GPW < args.nmsg; wv += nwaves) {
+        // The message's index where a run's end value is stored, worked out
+        // again from the wave's index and the lane: held across the pieces it
+        // cost the 32-lane build two registers it does not have.
+        auto message = [&] {
+            uint32_t t = threadIdx.x;
+            asm volatile("" : "+v"(t));  // no instruction; not merged with the m below
+            return wv * GPW + (t & 63u) / G;
+        };
+        const uint64_t m = wv * GPW + grp;
+        const bool active = m < args.nmsg;
+        IovCursor<false> s;
+        s.begin(args.src, 0, 0);
+        if (active) s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
+        uint64_t reg = ~0ull;  // seed 0 (crc.cpp:119-122)
+        // One piece of n bytes at the source cursor, which moves before the
+        // rows (as in crc64_copy_iov_kernel); the register is broadcast within
+        // the group.
+        auto piece = [&](uint64_t n, CopyTo ct) {
+            const uint8_t* sp = s.p;
+            s.p += n;
+            s.rem -= n;
+            const uint64_t r = buffer_reg64<G, true, 3>(lds, sp, n, reg, gl, lane, la, true, ct);
+            const uint64_t v = gl == 0 ? r : 0ull;
+            reg = ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+        };
+        auto seg_end = [&] {  // the running CRC at the end of source segment s.i
+            if (!s.rem) {
+                if (gl == 0) args.src_seg[s.i] = ~reg;
+                s.next();
+            }
+        };
+        auto skim = [&](uint64_t cnt) {  // up to cnt source bytes, none stored
+            while (cnt && s.more()) {
+                const uint64_t n = s.rem < cnt ? s.rem : cnt;
+                cnt -= n;
+                piece(n, CopyTo{});
+                seg_end();
+            }
+        };
+        skim(active && args.skip ? args.skip[m] : 0ull);
+        uint64_t left = 0;
+        IovCursor<false> d;
+        d.begin(args.dst, 0, 0);
+        if (active) {
+            const uint64_t mm = message();
+            if (gl == 0) args.work[2 * mm] = ~reg;  // R(a)
+            left = args.size ? args.size[mm] : ~0ull;
+            d.begin(args.dst, args.dst_start[mm], args.dst_start[mm + 1]);
+        }
+        while (left && s.more() && d.more()) {
+            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
+            n = n < left ? n : left;
+            const CopyTo ct = copy_begin<G>(s.p, const_cast<uint8_t*>(d.p), n, gl);
+            d.p += n;
+            d.rem -= n;
+            left -= n;
+            piece(n, ct);
+            if (!left) break;
+            seg_end();
+            if (!d.rem) d.next();
+        }
+        {
+            const uint64_t mm = message();
+            if (mm < args.nmsg && gl == 0) args.work[2 * mm + 1] = ~reg;  // R(b)
+        }
+        skim(~0ull);
+    }
+}
+
 // ------------------------------------------------ full-row uniform batches
 // Strided batches whose buffers are made of whole steps: base and stride
 // 16-byte aligned, nbytes a multiple of 2 * 16 G U (an even number of U-row
