@@ -182,6 +182,19 @@ int photon_crc_test_small_plan(uint64_t addr, uint64_t n, int crc64, uint64_t* o
  * it. The lane-group size follows the piece size by the batch kernels' rule. */
 int photon_crc_set_parts_piece(uint64_t bytes);
 
+/* Span of a staging chunk of photon_crc32c_host_batch_strided /
+ * photon_crc64ecma_host_batch_strided (testing): 0 = the default (the whole
+ * 256 MiB staging allocation), else a multiple of 256 from 64 KiB to 256 MiB.
+ * A chunk takes max(1, span / pitch) buffers, so a few MiB of payload run
+ * through many chunks and reuse every staging slot. The allocations stay
+ * 256 MiB, and a buffer above 256 MiB is refused as before. */
+int photon_crc_set_host_stage_bytes(uint64_t bytes);
+
+/* Payload span per chunk of photon_crc32c_file_strided (testing): 0 = the
+ * default (64 MiB), else a multiple of 4 KiB from 4 KiB to 64 MiB. A chunk
+ * takes max(1, span / stride) records. */
+int photon_crc_set_file_chunk_bytes(uint64_t bytes);
+
 /* The cut of ONE part of `len` bytes at address `addr` (not dereferenced)
  * under the cap max_part_bytes, in pieces of `piece` bytes (0 = the current
  * setting), exactly as the piece kernels derive it

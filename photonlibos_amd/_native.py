@@ -136,6 +136,8 @@ def _declare(L):
     fn("photon_crc64ecma_batch_parts_n", ctypes.c_int, vp, u64, u64, u64, vp, vp, vp, u64, vp)
     fn("photon_crc_parts_work_bytes", u64, u64, u64, ctypes.c_int)
     fn("photon_crc_set_parts_piece", ctypes.c_int, u64)
+    fn("photon_crc_set_host_stage_bytes", ctypes.c_int, u64)
+    fn("photon_crc_set_file_chunk_bytes", ctypes.c_int, u64)
     fn("photon_crc_util_parts_fold", ctypes.c_int, ctypes.c_int, vp, u64, u64, u64, vp, vp, vp, vp)
     fn("photon_crc_test_parts_plan", ctypes.c_int, u64, u64, u64, u64, vp, ctypes.c_int)
     fn("photon_crc32c_copy_parts_packed_n", ctypes.c_int, vp, vp, u64, u64, u64, u32, vp, vp, vp, vp, u64, vp)

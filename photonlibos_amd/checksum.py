@@ -36,7 +36,7 @@ __all__ = [
     "copy_msg_iov_window_n", "copy_msg64_iov_window_n", "window_work_bytes",
     "copy_extend_device", "copy_extend64_device",
     "copy_parts_device", "copy_parts64_device", "batch_parts_device", "batch_parts64_device", "parts_work_bytes",
-    "set_parts_piece",
+    "set_parts_piece", "set_host_stage_bytes", "set_file_chunk_bytes",
     "copy_parts_packed_device", "copy_parts64_packed_device", "batch_parts_packed_device",
     "batch_parts64_packed_device", "parts_packed_work_bytes",
     "series64_device", "combine_series64_device", "fold_parts_device", "fold_parts64_device",
@@ -590,6 +590,18 @@ def parts_work_bytes(nparts, max_part_bytes, crc64=False):
 def set_parts_piece(nbytes):
     """Piece size of the parts calls: 0 = automatic (32 KiB), else a multiple of 4 KiB (tuning.h)."""
     _check(lib().photon_crc_set_parts_piece(nbytes))
+
+
+def set_host_stage_bytes(nbytes):
+    """Span of a staging chunk of the host-memory pipeline: 0 = the default (256 MiB), else a multiple of
+    256 from 64 KiB to 256 MiB (tuning.h; tests reach the reuse of the staging slots with it)."""
+    _check(lib().photon_crc_set_host_stage_bytes(nbytes))
+
+
+def set_file_chunk_bytes(nbytes):
+    """Payload span per chunk of file_strided: 0 = the default (64 MiB), else a multiple of 4 KiB up to
+    64 MiB (tuning.h; tests reach the reuse of the two chunk buffers with it)."""
+    _check(lib().photon_crc_set_file_chunk_bytes(nbytes))
 
 
 def _work_bytes(work, work_bytes):

@@ -62,6 +62,7 @@
 #include "overwrite_kernels.h"
 #include "long_plan.h"
 #include "multi_device.h"
+#include "host_chunks.h"
 #include "gf2.h"
 #include "internal.h"
 
@@ -958,9 +959,11 @@ int launch_copy_iov_window(const CopyIovWindow64Args& a, int g, hipStream_t stre
 // Host-memory pipeline (photon_crc32c_host_batch_strided): per device, a copy
 // stream and a compute stream, kNumStage device staging chunks. Chunk i is
 // copied (H2D, 2-D so any host stride packs densely) while chunk i-1 is
-// checksummed; events order reuse of a staging chunk after its kernel.
-constexpr int kNumStage = 3;
-constexpr uint64_t kStageBytes = 256ull << 20;
+// checksummed; events order reuse of a staging chunk after its kernel. The
+// chunk arithmetic (kNumStage, kStageBytes, stage_plan) is host_chunks.h's.
+// g_host_stage: the span of a staging chunk the pipeline fills, 0 = the whole
+// allocation (photon_crc_set_host_stage_bytes; tests reach slot reuse with it).
+std::atomic<uint64_t> g_host_stage{0};
 
 struct HostPipe {
     std::mutex mu;  // one host-memory batch at a time per device; devices run concurrently
@@ -2388,8 +2391,11 @@ int host_batch_impl(const void* h_base, uint64_t stride, uint64_t nbytes, uint64
         for (uint64_t i = 0; i < count; ++i) h_out[i] = h_seeds ? h_seeds[i] : seed0;
         return 0;
     }
-    const uint64_t pitch = (nbytes + 255) & ~uint64_t(255);
-    if (pitch > kStageBytes) return fail(-EINVAL, "buffer larger than a staging chunk (256 MiB)");
+    // pitch > kStageBytes, asked of nbytes (kStageBytes is a multiple of 256) so that no size wraps the pitch
+    if (nbytes > kStageBytes) return fail(-EINVAL, "buffer larger than a staging chunk (256 MiB)");
+    const uint64_t span = g_host_stage.load(std::memory_order_relaxed);
+    const StagePlan pl = stage_plan(nbytes, count, span ? span : kStageBytes);
+    const uint64_t pitch = pl.pitch;
     int cus = 0;
     int dev = current_device(&cus);
     if (dev < 0) return dev;
@@ -2426,11 +2432,11 @@ int host_batch_impl(const void* h_base, uint64_t stride, uint64_t nbytes, uint64
         e = hipMemcpyAsync(d_seeds, h_seeds, bytes, hipMemcpyHostToDevice, p->comp);
         if (e != hipSuccess) return hip_fail(e, "seeds H2D");
     }
-    const uint64_t per_chunk = kStageBytes / pitch;
     const uint8_t* src = static_cast<const uint8_t*>(h_base);
-    for (uint64_t first = 0, i = 0; first < count; first += per_chunk, ++i) {
-        const int slot = (int)(i % kNumStage);
-        const uint64_t k = count - first < per_chunk ? count - first : per_chunk;
+    for (uint64_t i = 0; i < pl.nchunks; ++i) {
+        const StageChunk ch = stage_chunk(pl, i);
+        const int slot = ch.slot;
+        const uint64_t first = ch.first, k = ch.k;
         if ((e = hipStreamWaitEvent(p->copy, p->consumed[slot], 0)) != hipSuccess) return hip_fail(e, "wait");
         e = hipMemcpy2DAsync(p->stage[slot], pitch, src + first * stride, stride, nbytes, k, hipMemcpyHostToDevice,
                              p->copy);
@@ -3196,6 +3202,13 @@ uint64_t photon_crc_parts_work_bytes(uint64_t nparts, uint64_t max_part_bytes, i
     PartsPlan pl;
     if (!parts_plan(nparts, max_part_bytes, parts_piece_now(), &pl)) return ~0ull;
     return pl.ntasks * (crc64 ? sizeof(uint64_t) : sizeof(uint32_t));
+}
+
+int photon_crc_set_host_stage_bytes(uint64_t bytes) {
+    if (!stage_span_valid(bytes))
+        return fail(-EINVAL, "host stage bytes: 0 (default) or a multiple of 256 from 64 KiB to 256 MiB");
+    g_host_stage.store(bytes, std::memory_order_relaxed);
+    return 0;
 }
 
 int photon_crc_set_parts_piece(uint64_t bytes) {
