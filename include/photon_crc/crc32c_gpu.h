@@ -950,6 +950,85 @@ int photon_crc64ecma_patch_n(const uint64_t* d_delta, const uint64_t* d_tail, ui
                              const uint64_t* d_tgt_start, uint64_t ntgt, const uint64_t* d_crc_in, uint64_t* d_crc_out,
                              void* stream);
 
+/* Stripe parity + CRC in one read: the XOR parity of a
+ * stripe of k equal-length blocks (RAID-5 style, k data blocks plus one
+ * parity), and its mirror, the rebuild of a lost block from the survivors.
+ * Stripe s has k sources of n_s bytes:
+ *   strided: source i = src_base + s*stripe_stride + i*block_stride, n_s =
+ *            nbytes, parity s = d_dst_base + s*dst_stride;
+ *   ptr:     source i = d_src[s*k + i] (count*k device-resident pointers,
+ *            stripe-major), d_dst[s] = {parity address, n_s}.
+ * After the call the n_s bytes at parity s hold P_s, the byte-wise XOR of the
+ * stripe's sources, and
+ *   d_out[s] = crc32c_extend(P_s, n_s, seed_s)   (CRC-64: crc64ecma_extend),
+ * the ordinary CRC of the parity bytes with the usual seed rule (d_seeds[s],
+ * or seed0 when d_seeds is null), computed from the very registers that are
+ * stored. 1 <= k <= 64, else -EINVAL; k = 1 is copy + CRC. In the ptr form a
+ * NULL source pointer is an all-zero block that is not read (the short last
+ * stripe of an object); a stripe whose sources are all NULL writes n_s zero
+ * bytes and returns the CRC of n_s zero bytes from the seed. n_s == 0 writes
+ * nothing and returns the seed.
+ * Both CRCs are affine, so d_out[s] must equal the XOR of the sources' stored
+ * CRCs (plus a zero-run term for an even count): photon_crc32c_xor_expect_n
+ * below computes that word, and photon_crc32c_verify_n on the two arrays is
+ * an end-to-end check of all k source reads. A rebuild is the same call:
+ * sources = the k-1 survivors plus the parity, destination = the lost block,
+ * and d_out[s] is compared with the lost block's stored word.
+ * Contract (iv) of the copy calls applies unchanged: sources are HBM, or
+ * pinned / registered host memory; no byte outside [dst, dst + n) is written;
+ * null arrays with a non-zero count give -EINVAL ("null ..." in
+ * photon_crc_last_error()); count == 0 returns 0 and touches nothing;
+ * asynchronous on `stream`, nothing allocated or synchronised; plain stores
+ * only and no atomics: capturable and replayable; no CPU fallback.
+ * Overlap: two parity ranges must not overlap (the caller's duty). A parity
+ * range may coincide EXACTLY, same address and length, with ONE source of its
+ * own stripe: the in-place accumulate P ^= D, or the RAID-5 small write
+ * P' = P ^ D_old ^ D_new with k = 3. Any other overlap of a parity with a
+ * source is the caller's error.
+ * Every source byte is read once and every parity byte written once when all
+ * non-null sources of a stripe and its parity are congruent modulo 16, or
+ * n_s < 64; any other stripe is correct, with no performance claim (the parity
+ * is landed byte by byte and then checksummed from the cache).
+ * photon_crc_set_lanes_per_buffer and photon_crc_set_batch_grid apply as to
+ * the copy calls; the rows knobs do not. */
+int photon_crc32c_xor_batch_strided(const void* src_base, uint64_t stripe_stride, uint64_t block_stride, uint32_t k,
+                                    void* d_dst_base, uint64_t dst_stride, uint64_t nbytes, uint64_t count,
+                                    uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_out, void* stream);
+int photon_crc32c_xor_batch_ptr(const void* const* d_src, uint32_t k, const photon_crc_iovec* d_dst, uint64_t count,
+                                uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_out, void* stream);
+int photon_crc64ecma_xor_batch_strided(const void* src_base, uint64_t stripe_stride, uint64_t block_stride, uint32_t k,
+                                       void* d_dst_base, uint64_t dst_stride, uint64_t nbytes, uint64_t count,
+                                       uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out, void* stream);
+int photon_crc64ecma_xor_batch_ptr(const void* const* d_src, uint32_t k, const photon_crc_iovec* d_dst,
+                                   uint64_t count, uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out,
+                                   void* stream);
+
+/* The CRC a stripe's parity must have, from stored block CRCs alone, no
+ * payload read. Group s = the words [d_grp_start[s],
+ * d_grp_start[s+1]) of d_crc, or [s*k, (s+1)*k) with a null d_grp_start (then
+ * 1 <= k <= 64); both ends are clamped into [0, ncrc], so whatever the array
+ * holds nothing outside d_crc is read. n_s = d_len ? d_len[s] : nbytes (64-bit
+ * lengths). With m = the group's size,
+ *   d_want[s] = XOR of the group's words ^ (m even ? crc_extend(n_s zero bytes, seed) : 0),
+ * the CRC from `seed` of the XOR of those blocks when every stored word was
+ * taken from `seed`. An empty group gives the CRC of n_s zero bytes; a NULL
+ * source of the call above is simply left out of its group. Behind that call
+ * on the same stream with no synchronisation, photon_crc32c_verify_n(d_out,
+ * d_want, ...) reports the stripes whose sources do not match their stored
+ * CRCs (batch_* plus verify_n then say which source); for a rebuild,
+ * verify_n(d_out, the lost block's stored word) accepts or rejects the
+ * rebuilt bytes.
+ * count == 0 returns 0 and touches nothing; a null d_want, a null d_crc with
+ * ncrc > 0, or a null d_grp_start with k outside 1..64 gives -EINVAL ("null
+ * ..."); one launch, a thread per stripe, no workspace, plain stores only:
+ * capturable and replayable. */
+int photon_crc32c_xor_expect_n(const uint32_t* d_crc, uint64_t ncrc, const uint64_t* d_grp_start, uint32_t k,
+                               const uint64_t* d_len, uint64_t nbytes, uint64_t count, uint32_t seed,
+                               uint32_t* d_want, void* stream);
+int photon_crc64ecma_xor_expect_n(const uint64_t* d_crc, uint64_t ncrc, const uint64_t* d_grp_start, uint32_t k,
+                                  const uint64_t* d_len, uint64_t nbytes, uint64_t count, uint64_t seed,
+                                  uint64_t* d_want, void* stream);
+
 /* Runtime shim so that Photon code drives the batches without HIP headers
  * (host code stays Photon C++; HIP stays behind this library):
  *   stream_create / _destroy / _sync: a non-blocking stream of the current

@@ -255,6 +255,20 @@ int photon_crc_test_patch(int crc64, const void* delta, const uint64_t* tail, ui
                           const uint64_t* tgt_start, uint64_t ntgt, const void* crc_in, void* crc_out,
                           uint32_t nthreads);
 
+/* CPU replay of the expect kernel (photon_crc32c_xor_expect_n /
+ * photon_crc64ecma_xor_expect_n; photonlibos_amd/csrc/xor_expect.h): the
+ * kernel's per-stripe step run on the host. Arguments as the device calls',
+ * every array host memory; crc and want are uint64_t words if crc64, else
+ * uint32_t (and the seed's low 32 bits are used). Returns 0, or -EINVAL. */
+int photon_crc_test_xor_expect(int crc64, const void* crc, uint64_t ncrc, const uint64_t* grp_start, uint32_t k,
+                               const uint64_t* len, uint64_t nbytes, uint64_t count, uint64_t seed, void* want);
+
+/* Build constants of the stripe parity kernels (photon_crc32c_xor_batch_*,
+ * DESIGN.md §4.16): sources whose loads are issued together per row, rows per
+ * step of the CRC-32C and of the CRC-64 builds, and the most sources a stripe
+ * may have. Null pointers are skipped. Returns 0. */
+int photon_crc_xor_geometry(int* in_flight, int* rows_per_step, int* rows_per_step64, int* max_sources);
+
 /* Bench utility (scripts/bench_copy_crc.py --fold, arm (a)): the route a
  * caller took before photon_crc32c_fold_parts_n / photon_crc64ecma_fold_parts_n
  * existed, natively: photon_crc_stream_sync(stream), the nparts part CRCs at

@@ -173,6 +173,14 @@ def _declare(L):
     fn("photon_crc32c_patch_n", ctypes.c_int, vp, vp, u64, vp, u64, vp, vp, vp)
     fn("photon_crc64ecma_patch_n", ctypes.c_int, vp, vp, u64, vp, u64, vp, vp, vp)
     fn("photon_crc_test_patch", ctypes.c_int, ctypes.c_int, vp, vp, u64, vp, u64, vp, vp, u32)
+    fn("photon_crc32c_xor_batch_strided", ctypes.c_int, vp, u64, u64, u32, vp, u64, u64, u64, u32, vp, vp, vp)
+    fn("photon_crc32c_xor_batch_ptr", ctypes.c_int, vp, u32, vp, u64, u32, vp, vp, vp)
+    fn("photon_crc64ecma_xor_batch_strided", ctypes.c_int, vp, u64, u64, u32, vp, u64, u64, u64, u64, vp, vp, vp)
+    fn("photon_crc64ecma_xor_batch_ptr", ctypes.c_int, vp, u32, vp, u64, u64, vp, vp, vp)
+    fn("photon_crc32c_xor_expect_n", ctypes.c_int, vp, u64, vp, u32, vp, u64, u64, u32, vp, vp)
+    fn("photon_crc64ecma_xor_expect_n", ctypes.c_int, vp, u64, vp, u32, vp, u64, u64, u64, vp, vp)
+    fn("photon_crc_test_xor_expect", ctypes.c_int, ctypes.c_int, vp, u64, vp, u32, vp, u64, u64, u64, vp)
+    fn("photon_crc_xor_geometry", ctypes.c_int, vp, vp, vp, vp)
     # include/photon_crc/checked_batch.h
     fn("photon_crc_pinned_allocate", ctypes.c_int, vp, PhotonRange, ctypes.POINTER(vp))
     fn("photon_crc_pinned_deallocate", ctypes.c_int, vp, vp)

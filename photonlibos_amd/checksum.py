@@ -42,6 +42,8 @@ __all__ = [
     "series64_device", "combine_series64_device", "fold_parts_device", "fold_parts64_device",
     "overwrite_batch_strided", "overwrite_batch_iov", "overwrite_batch64_strided", "overwrite_batch64_iov",
     "patch_device", "patch64_device",
+    "xor_batch_strided", "xor_batch_ptr", "xor_batch64_strided", "xor_batch64_ptr",
+    "xor_expect_device", "xor_expect64_device",
     "crc64ecma_series_at", "crc64ecma_combine_series_at",
     "scan_work_bytes", "set_scan_tile", "scan_parts_device", "scan_parts64_device",
     "VerifyReport", "verify_work_bytes", "set_verify_tile",
@@ -759,6 +761,54 @@ def patch64_device(delta, tail, nwrites, tgt_start, ntgt, crc_in, crc_out, strea
     """patch_device for CRC-64/ECMA (uint64 delta / crc_in / crc_out). Async, capturable."""
     _check(lib().photon_crc64ecma_patch_n(_ptr(delta), _ptr(tail), nwrites, _ptr(tgt_start), ntgt, _ptr(crc_in),
                                           _ptr(crc_out), _stream(stream)))
+
+
+def xor_batch_strided(src, stripe_stride, block_stride, k, dst, dst_stride, nbytes, count, out, seed=0, seeds=None,
+                      stream=None):
+    """Stripe parity + CRC-32C in one read: dst + s*dst_stride receives the byte-wise XOR of the k
+    blocks src + s*stripe_stride + i*block_stride (nbytes each), and out[s] (uint32) =
+    crc32c_extend(parity, nbytes, seed_s). 1 <= k <= 64. A parity may coincide exactly with one
+    source of its own stripe (P ^= D). Async, capturable."""
+    _check(lib().photon_crc32c_xor_batch_strided(_ptr(src), stripe_stride, block_stride, k, _ptr(dst), dst_stride,
+                                                 nbytes, count, seed, _ptr(seeds), _ptr(out), _stream(stream)))
+
+
+def xor_batch_ptr(src_ptrs, k, dst_iov, count, out, seed=0, seeds=None, stream=None):
+    """xor_batch_strided over pointers: stripe s XORs the blocks at src_ptrs[s*k .. s*k+k-1] (a
+    device array of pointers; a null pointer is an all-zero block that is not read) into
+    dst_iov[s].base, dst_iov[s].len bytes each. A rebuild is the same call with the survivors and
+    the parity as sources. Async, capturable."""
+    _check(lib().photon_crc32c_xor_batch_ptr(_ptr(src_ptrs), k, _ptr(dst_iov), count, seed, _ptr(seeds), _ptr(out),
+                                             _stream(stream)))
+
+
+def xor_batch64_strided(src, stripe_stride, block_stride, k, dst, dst_stride, nbytes, count, out, seed=0, seeds=None,
+                        stream=None):
+    """xor_batch_strided for CRC-64/ECMA (uint64 seeds / out). Async, capturable."""
+    _check(lib().photon_crc64ecma_xor_batch_strided(_ptr(src), stripe_stride, block_stride, k, _ptr(dst), dst_stride,
+                                                    nbytes, count, seed, _ptr(seeds), _ptr(out), _stream(stream)))
+
+
+def xor_batch64_ptr(src_ptrs, k, dst_iov, count, out, seed=0, seeds=None, stream=None):
+    """xor_batch_ptr for CRC-64/ECMA (uint64 seeds / out). Async, capturable."""
+    _check(lib().photon_crc64ecma_xor_batch_ptr(_ptr(src_ptrs), k, _ptr(dst_iov), count, seed, _ptr(seeds), _ptr(out),
+                                                _stream(stream)))
+
+
+def xor_expect_device(crcs, ncrc, grp_start, k, lens, nbytes, count, want, seed=0, stream=None):
+    """The CRC-32C a stripe's XOR parity must have, from the stored CRCs of its blocks alone:
+    want[s] = XOR of crcs[grp_start[s] .. grp_start[s+1]-1] (grp_start None: k words per stripe)
+    ^ (group size even ? crc32c_extend(n_s zero bytes, seed) : 0), n_s = lens[s] (uint64) or
+    nbytes when lens is None. Compare with xor_batch_*'s out through verify_device. Async,
+    capturable."""
+    _check(lib().photon_crc32c_xor_expect_n(_ptr(crcs), ncrc, _ptr(grp_start), k, _ptr(lens), nbytes, count, seed,
+                                            _ptr(want), _stream(stream)))
+
+
+def xor_expect64_device(crcs, ncrc, grp_start, k, lens, nbytes, count, want, seed=0, stream=None):
+    """xor_expect_device for CRC-64/ECMA (uint64 crcs / seed / want). Async, capturable."""
+    _check(lib().photon_crc64ecma_xor_expect_n(_ptr(crcs), ncrc, _ptr(grp_start), k, _ptr(lens), nbytes, count, seed,
+                                               _ptr(want), _stream(stream)))
 
 
 def scan_work_bytes(nparts):

@@ -60,6 +60,7 @@
 #include "crc32c_kernels.h"
 #include "crc64_kernels.h"
 #include "overwrite_kernels.h"
+#include "xor_kernels.h"
 #include "long_plan.h"
 #include "multi_device.h"
 #include "host_chunks.h"
@@ -838,6 +839,40 @@ int launch_overwrite(const OverwriteArgs<uint64_t>& a, int g, hipStream_t stream
                                [&](auto G, dim3 grid, const LaneConsts64& kc) {
         constexpr int GG = decltype(G)::value;
         hipLaunchKernelGGL((crc64_overwrite_kernel<GG, overwrite_rows(GG)>), grid, dim3(kBlock), 0, stream, a, kc);
+    });
+}
+
+// The stripe parity + CRC kernels (crc32c_xor_kernel<G, U>, crc64_xor_kernel<G, U>;
+// DESIGN.md §4.16): one build per lane-group size (the rows knobs do not apply;
+// photon_crc_set_lanes_per_buffer and photon_crc_set_batch_grid do). A row
+// costs 4 VGPRs of accumulator and 4 * kXorInFlight of loads in flight. With 4
+// loads in flight the CRC-32C builds take 2 rows per step (85 to 115 VGPRs);
+// the CRC-64 builds, whose table steps hold twice the registers, spill at 2
+// rows for every lane group below 64 and take 1 (89 to 111 VGPRs): every build
+// stays inside the 128 VGPRs of one 1,024-thread workgroup per CU without
+// scratch.
+#ifndef PCRC_XOR_ROWS  // A/B builds (the Makefile's EXTRA)
+#define PCRC_XOR_ROWS 2
+#endif
+#ifndef PCRC_XOR_ROWS64
+#define PCRC_XOR_ROWS64 1
+#endif
+constexpr int xor_rows(int /*g*/) { return PCRC_XOR_ROWS; }
+constexpr int xor_rows64(int /*g*/) { return PCRC_XOR_ROWS64; }
+
+int launch_xor(const XorArgs<uint32_t>& a, int g, hipStream_t stream) {
+    return launch_lanes<Crc32c>(a.count, g, true, stream, "crc32c_xor_kernel launch",
+                                [&](auto G, dim3 grid, const LaneConsts& kc) {
+        constexpr int GG = decltype(G)::value;
+        hipLaunchKernelGGL((crc32c_xor_kernel<GG, xor_rows(GG)>), grid, dim3(kBlock), 0, stream, a, kc);
+    });
+}
+
+int launch_xor(const XorArgs<uint64_t>& a, int g, hipStream_t stream) {
+    return launch_lanes<Crc64>(a.count, g, true, stream, "crc64_xor_kernel launch",
+                               [&](auto G, dim3 grid, const LaneConsts64& kc) {
+        constexpr int GG = decltype(G)::value;
+        hipLaunchKernelGGL((crc64_xor_kernel<GG, xor_rows64(GG)>), grid, dim3(kBlock), 0, stream, a, kc);
     });
 }
 
@@ -1828,6 +1863,83 @@ int patch_n(const typename W::T* d_delta, const uint64_t* d_tail, uint64_t nwrit
                        d_crc_out, pow_table<W>());
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, "_patch_kernel launch");
+}
+
+// Stripe parity + CRC (crc32c_gpu.h):
+// photon_crc32c_xor_batch_strided / photon_crc64ecma_xor_batch_strided.
+// Lanes as the copy calls take them (W::copy_lanes).
+template <typename W>
+int xor_batch_strided(const void* src_base, uint64_t stripe_stride, uint64_t block_stride, uint32_t k,
+                      void* d_dst_base, uint64_t dst_stride, uint64_t nbytes, uint64_t count, typename W::T seed0,
+                      const typename W::T* d_seeds, typename W::T* d_out, void* stream) {
+    if (!count) return 0;
+    if (k < 1 || k > kXorMaxSources) return fail(-EINVAL, "a stripe has 1 to 64 sources");
+    if (!d_out || ((!src_base || !d_dst_base) && nbytes)) return fail(-EINVAL, "null source, parity or CRC output");
+    XorArgs<typename W::T> a{};
+    a.base = static_cast<const uint8_t*>(src_base);
+    a.stripe_stride = stripe_stride;
+    a.block_stride = block_stride;
+    a.nbytes = nbytes;
+    a.dst_base = static_cast<uint8_t*>(d_dst_base);
+    a.dst_stride = dst_stride;
+    a.k = k;
+    a.count = count;
+    a.seed0 = seed0;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    return launch_xor(a, W::copy_lanes(nbytes), static_cast<hipStream_t>(stream));
+}
+
+// photon_crc32c_xor_batch_ptr / photon_crc64ecma_xor_batch_ptr.
+template <typename W>
+int xor_batch_ptr(const void* const* d_src, uint32_t k, const photon_crc_iovec* d_dst, uint64_t count,
+                  typename W::T seed0, const typename W::T* d_seeds, typename W::T* d_out, void* stream) {
+    if (!count) return 0;
+    if (k < 1 || k > kXorMaxSources) return fail(-EINVAL, "a stripe has 1 to 64 sources");
+    if (!d_src || !d_dst || !d_out) return fail(-EINVAL, "null source pointer array, parity descriptors or CRC output");
+    XorArgs<typename W::T> a{};
+    a.src = d_src;
+    a.dstv = d_dst;
+    a.k = k;
+    a.count = count;
+    a.seed0 = seed0;
+    a.seeds = d_seeds;
+    a.out = d_out;
+    return launch_xor(a, W::copy_lanes(65536), static_cast<hipStream_t>(stream));
+}
+
+// The inversion of the register on the way in and out (xor_expect.h).
+template <typename W>
+constexpr typename W::T xor_expect_inv() {
+    return sizeof(typename W::T) == 8 ? ~(typename W::T)0 : 0;
+}
+
+bool xor_expect_args_ok(const void* crc, uint64_t ncrc, const uint64_t* grp_start, uint32_t k, const void* want) {
+    if (!want) return false;
+    if (!crc && ncrc) return false;
+    return grp_start || (k >= 1 && k <= kXorMaxSources);
+}
+constexpr const char* kXorExpectArgs =
+    "null words with ncrc > 0, null output, or a null d_grp_start with k outside 1 to 64";
+
+// photon_crc32c_xor_expect_n / photon_crc64ecma_xor_expect_n: one launch, a
+// thread per stripe.
+template <typename W>
+int xor_expect_n(const typename W::T* d_crc, uint64_t ncrc, const uint64_t* d_grp_start, uint32_t k,
+                 const uint64_t* d_len, uint64_t nbytes, uint64_t count, typename W::T seed, typename W::T* d_want,
+                 void* stream) {
+    if (!count) return 0;
+    if (!xor_expect_args_ok(d_crc, ncrc, d_grp_start, k, d_want)) return fail(-EINVAL, kXorExpectArgs);
+    int cus = 0;
+    int dev = current_device(&cus);
+    if (dev < 0) return dev;
+    const uint64_t blocks = (count + kXorExpectBlock - 1) / kXorExpectBlock;
+    const uint32_t grid = blocks < kFoldMaxGrid ? (uint32_t)blocks : kFoldMaxGrid;
+    hipLaunchKernelGGL((xor_expect_kernel<W, typename W::Pow>), dim3(grid), dim3(kXorExpectBlock), 0,
+                       static_cast<hipStream_t>(stream), d_crc, ncrc, d_grp_start, k, d_len, nbytes, count, seed,
+                       xor_expect_inv<W>(), d_want, pow_table<W>());
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, W::kKernel, "_xor_expect_kernel launch");
 }
 
 // ------------------------------------- running CRCs of an object's parts
@@ -2989,6 +3101,67 @@ int photon_crc_test_patch(int crc64, const void* delta, const uint64_t* tail, ui
         patch_replay<Gf32>(static_cast<const uint32_t*>(delta), tail, nwrites, tgt_start, ntgt,
                            static_cast<const uint32_t*>(crc_in), static_cast<uint32_t*>(crc_out), nthreads,
                            pow_table<Crc32c>().x8pow2);
+    return 0;
+}
+
+int photon_crc32c_xor_batch_strided(const void* src_base, uint64_t stripe_stride, uint64_t block_stride, uint32_t k,
+                                    void* d_dst_base, uint64_t dst_stride, uint64_t nbytes, uint64_t count,
+                                    uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_out, void* stream) {
+    return xor_batch_strided<Crc32c>(src_base, stripe_stride, block_stride, k, d_dst_base, dst_stride, nbytes, count,
+                                     seed0, d_seeds, d_out, stream);
+}
+
+int photon_crc32c_xor_batch_ptr(const void* const* d_src, uint32_t k, const photon_crc_iovec* d_dst, uint64_t count,
+                                uint32_t seed0, const uint32_t* d_seeds, uint32_t* d_out, void* stream) {
+    return xor_batch_ptr<Crc32c>(d_src, k, d_dst, count, seed0, d_seeds, d_out, stream);
+}
+
+int photon_crc64ecma_xor_batch_strided(const void* src_base, uint64_t stripe_stride, uint64_t block_stride, uint32_t k,
+                                       void* d_dst_base, uint64_t dst_stride, uint64_t nbytes, uint64_t count,
+                                       uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out, void* stream) {
+    return xor_batch_strided<Crc64>(src_base, stripe_stride, block_stride, k, d_dst_base, dst_stride, nbytes, count,
+                                    seed0, d_seeds, d_out, stream);
+}
+
+int photon_crc64ecma_xor_batch_ptr(const void* const* d_src, uint32_t k, const photon_crc_iovec* d_dst,
+                                   uint64_t count, uint64_t seed0, const uint64_t* d_seeds, uint64_t* d_out,
+                                   void* stream) {
+    return xor_batch_ptr<Crc64>(d_src, k, d_dst, count, seed0, d_seeds, d_out, stream);
+}
+
+int photon_crc32c_xor_expect_n(const uint32_t* d_crc, uint64_t ncrc, const uint64_t* d_grp_start, uint32_t k,
+                               const uint64_t* d_len, uint64_t nbytes, uint64_t count, uint32_t seed,
+                               uint32_t* d_want, void* stream) {
+    return xor_expect_n<Crc32c>(d_crc, ncrc, d_grp_start, k, d_len, nbytes, count, seed, d_want, stream);
+}
+
+int photon_crc64ecma_xor_expect_n(const uint64_t* d_crc, uint64_t ncrc, const uint64_t* d_grp_start, uint32_t k,
+                                  const uint64_t* d_len, uint64_t nbytes, uint64_t count, uint64_t seed,
+                                  uint64_t* d_want, void* stream) {
+    return xor_expect_n<Crc64>(d_crc, ncrc, d_grp_start, k, d_len, nbytes, count, seed, d_want, stream);
+}
+
+// tuning.h: the expect kernel's per-stripe step (xor_expect.h) on the host.
+int photon_crc_test_xor_expect(int crc64, const void* crc, uint64_t ncrc, const uint64_t* grp_start, uint32_t k,
+                               const uint64_t* len, uint64_t nbytes, uint64_t count, uint64_t seed, void* want) {
+    if (!count) return 0;
+    if (!xor_expect_args_ok(crc, ncrc, grp_start, k, want)) return fail(-EINVAL, kXorExpectArgs);
+    if (crc64)
+        xor_expect_replay<Gf64>(static_cast<const uint64_t*>(crc), ncrc, grp_start, k, len, nbytes, count, seed,
+                                xor_expect_inv<Crc64>(), static_cast<uint64_t*>(want), pow_table<Crc64>().x8pow2);
+    else
+        xor_expect_replay<Gf32>(static_cast<const uint32_t*>(crc), ncrc, grp_start, k, len, nbytes, count,
+                                (uint32_t)seed, xor_expect_inv<Crc32c>(), static_cast<uint32_t*>(want),
+                                pow_table<Crc32c>().x8pow2);
+    return 0;
+}
+
+// tuning.h: the stripe kernels' build constants.
+int photon_crc_xor_geometry(int* in_flight, int* rows_per_step, int* rows_per_step64, int* max_sources) {
+    if (in_flight) *in_flight = kXorInFlight;
+    if (rows_per_step) *rows_per_step = PCRC_XOR_ROWS;
+    if (rows_per_step64) *rows_per_step64 = PCRC_XOR_ROWS64;
+    if (max_sources) *max_sources = (int)kXorMaxSources;
     return 0;
 }
 
