@@ -10,6 +10,7 @@
 #include "../../include/photon_crc/crc32c_gpu.h"
 #include "fold_parts.h"
 #include "gf2.h"
+#include "iov_walk.h"
 #include "parts_packed_plan.h"
 #include "parts_plan.h"
 #include "scan_parts.h"
@@ -1276,11 +1277,9 @@ __global__ __launch_bounds__(kBlock) void crc32c_batch_kernel(std::conditional_t
 }
 
 // photon_crc32c_copy_msg_iov_n: copy + CRC between two
-// iovectors per message (iovector_view::memcpy_iov, iovector.cpp:301-318).
-// Message m: source segments src[src_start[m] .. src_start[m+1]), destination
-// segments dst[dst_start[m] .. dst_start[m+1]), at most size[m] bytes (no
-// size array: no cap). out[m] = the CRC of the copied bytes chained from
-// seed_m, copied[m] (optional) = their count.
+// iovectors per message (iovector_view::memcpy_iov, iovector.cpp:301-318): the
+// walk of iov_walk.h. out[m] = the CRC of the copied bytes chained from seed_m,
+// copied[m] (optional) = their count.
 struct CopyIovArgs {
     const photon_crc_iovec* src;
     const uint64_t* src_start;
@@ -1294,98 +1293,53 @@ struct CopyIovArgs {
     uint32_t seed0;
 };
 
-// One side of the two-cursor walk: the current segment's unconsumed part
-// [p, p + rem). PF: the NEXT segment's descriptor is loaded when the current
-// one is taken -- before the rows of the piece(s) that consume it, as the
-// message kernels prefetch theirs (the last one re-reads itself). Without PF
-// (builds where its four registers per side would spill) the descriptor is
-// loaded when it is needed, as crc64_gather_kernel loads its own.
-template <bool PF>
-struct IovCursor {
-    const photon_crc_iovec* v;
-    uint64_t i, end;           // the current segment and the message's last + 1
-    const uint8_t* p;
-    uint64_t rem;
-    photon_crc_iovec nx[PF ? 1 : 0];
-    __device__ __forceinline__ void take(const photon_crc_iovec& c) {
-        p = static_cast<const uint8_t*>(c.base);
-        rem = c.len;
-        if constexpr (PF) nx[0] = v[i + 1 < end ? i + 1 : i];
+// The CRC-32C copying unit of the two-cursor walk (iov_walk.h): a lane group's
+// place in the persistent grid, and one piece = copy_begin +
+// buffer_crc<G, U, PCRC_MSG_LEAD != 0, true>. The seed is used as given (the
+// register is the CRC), both sides prefetch their descriptors, and the
+// cursors advance after the rows.
+template <int G, int U>
+struct Unit32 {
+    typedef uint32_t T;
+    static constexpr int kGroups = 64 / G;
+    const uint32_t* lds;
+    uint32_t wave, gl, grp;
+    LaneAddr la;
+    __device__ __forceinline__ explicit Unit32(const uint32_t* tables) : lds(tables) {
+        const uint32_t lane = threadIdx.x & 63u;
+        wave = wave_id();
+        gl = lane & (G - 1);
+        grp = lane / G;
+        la = lane_addr(lane);
     }
-    __device__ __forceinline__ void begin(const photon_crc_iovec* iov, uint64_t s0, uint64_t s1) {
-        v = iov;
-        i = s0;
-        end = s1;
-        p = nullptr;
-        rem = 0;
-        if constexpr (PF) nx[0] = {nullptr, 0};
-        if (s0 < s1) take(iov[s0]);
+    __device__ __forceinline__ uint64_t first_wave() const { return (uint64_t)blockIdx.x * kWaves + wave; }
+    __device__ __forceinline__ uint64_t nwaves() const { return (uint64_t)gridDim.x * kWaves; }
+    // n bytes at the source cursor, stored where ct says (CopyTo{}: nowhere)
+    template <bool PF>
+    __device__ __forceinline__ T rows(IovCursor<PF>& s, uint64_t n, T reg, CopyTo ct) const {
+        reg = buffer_crc<G, U, PCRC_MSG_LEAD != 0, true>(lds, s.p, n, reg, gl, la, true, ct);
+        s.p += n;
+        s.rem -= n;
+        return reg;
     }
-    __device__ __forceinline__ bool more() const { return i < end; }
-    __device__ __forceinline__ void next() {  // rem == 0: the next segment
-        if (++i < end) {
-            if constexpr (PF) take(nx[0]);
-            else take(v[i]);
-        }
+    template <bool PS, bool PD>
+    __device__ __forceinline__ T copy(IovCursor<PS>& s, IovCursor<PD>& d, uint64_t& left, uint64_t n, T reg) const {
+        const CopyTo ct = copy_begin<G>(s.p, const_cast<uint8_t*>(d.p), n, gl);
+        reg = rows(s, n, reg, ct);
+        d.p += n;
+        d.rem -= n;
+        left -= n;
+        return reg;
     }
 };
 
-// One lane group per message, persistent grid and static split as the
-// message kernels. Each step is a piece of n = min(left, src.rem, dst.rem)
-// bytes through the copying unit (copy_begin + buffer_crc<.., COPY>),
-// chained through acc; then the side(s) that ran out take their next
-// segment -- both when the boundaries coincide, neither when the cap ended
-// the message. A zero-length segment on either side makes a zero-length
-// piece: tiny, no loads, no stores, acc unchanged (buf_finish), and only
-// that side advances.
+// The walk of iov_walk.h with Unit32 (a zero-length piece: tiny, no loads, no
+// stores, acc unchanged -- buf_finish).
 template <int G, int U>
 __global__ __launch_bounds__(kBlock) void crc32c_copy_iov_kernel(CopyIovArgs args, LaneConsts kc) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
-    constexpr bool kMsgLead = PCRC_MSG_LEAD != 0;
     load_tables<G>(lds, kc);
-
-    constexpr int GPW = 64 / G;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = wave_id();
-    const uint32_t gl = lane & (G - 1);
-    const uint32_t grp = lane / G;
-    const LaneAddr la = lane_addr(lane);
-
-    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
-    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave; wv * GPW < args.nmsg; wv += nwaves) {
-        const uint64_t m = wv * GPW + grp;
-        const bool active = m < args.nmsg;
-        uint32_t acc = args.seed0;
-        uint64_t left = 0;
-        IovCursor<true> s, d;
-        s.begin(args.src, 0, 0);
-        d.begin(args.dst, 0, 0);
-        if (active) {
-            left = args.size ? args.size[m] : ~0ull;
-            if (args.seeds) acc = args.seeds[m];
-            s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
-            d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
-        }
-        while (left && s.more() && d.more()) {
-            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
-            n = n < left ? n : left;
-            const CopyTo ct = copy_begin<G>(s.p, const_cast<uint8_t*>(d.p), n, gl);
-            acc = buffer_crc<G, U, kMsgLead, true>(lds, s.p, n, acc, gl, la, true, ct);
-            s.p += n;
-            d.p += n;
-            s.rem -= n;
-            d.rem -= n;
-            left -= n;
-            if (!left) break;
-            if (!s.rem) s.next();
-            if (!d.rem) d.next();
-        }
-        if (active && gl == 0) {
-            args.out[m] = acc;
-            // (the cap is read again: two registers less across the walk)
-            if (args.copied) args.copied[m] = (args.size ? args.size[m] : ~0ull) - left;
-        }
-    }
+    iov_copy_messages<false>(args, Unit32<G, U>(lds));
 }
 
 // photon_crc32c_copy_msg_iov_seg_n: the walk above, with one
@@ -1454,7 +1408,7 @@ struct SegFold {
     }
 };
 
-// DST: the chosen side. The piece loop is crc32c_copy_iov_kernel's; the
+// DST: the chosen side. The piece loop is iov_walk.h's; the
 // running value `sc` is chained through the seed from piece to piece within
 // a chosen-side segment and starts from 0 when that side's cursor takes a new
 // segment. When the cursor's rem reaches 0 the segment's CRC is final: the
@@ -1470,57 +1424,35 @@ struct SegFold {
 template <int G, int U, bool DST>
 __global__ __launch_bounds__(kBlock) void crc32c_copy_iov_seg_kernel(CopyIovSegArgs args, LaneConsts kc, PowTable pt) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
-    constexpr bool kMsgLead = PCRC_MSG_LEAD != 0;
     load_tables<G>(lds, kc);
-
-    constexpr int GPW = 64 / G;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = wave_id();
-    const uint32_t gl = lane & (G - 1);
-    const uint32_t grp = lane / G;
-    const LaneAddr la = lane_addr(lane);
+    const Unit32<G, U> u(lds);
+    const uint32_t gl = u.gl;
     SegFold<G> fold;
     fold.init();
 
-    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
-    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave; wv * GPW < args.nmsg; wv += nwaves) {
-        const uint64_t m = wv * GPW + grp;
+    iov_walk_messages(u, args.nmsg, [&](uint64_t m) PCRC_WALK_INLINE {
         const bool active = m < args.nmsg;
-        uint32_t acc = args.seed0;
-        uint64_t left = 0;
+        uint32_t acc;
+        uint64_t left;
         IovCursor<true> s, d;
-        s.begin(args.src, 0, 0);
-        d.begin(args.dst, 0, 0);
-        if (active) {
-            left = args.size ? args.size[m] : ~0ull;
-            if (args.seeds) acc = args.seeds[m];
-            s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
-            d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
-        }
+        iov_walk_begin(args, m, active, left, acc, s, d);
         IovCursor<true>& c = DST ? d : s;  // the chosen side
         uint32_t sc = 0;       // the current chosen-side segment's CRC so far
         uint64_t sl = 0;       // and how many of its bytes have landed
-        while (left && s.more() && d.more()) {
-            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
-            n = n < left ? n : left;
-            const CopyTo ct = copy_begin<G>(s.p, const_cast<uint8_t*>(d.p), n, gl);
-            sc = buffer_crc<G, U, kMsgLead, true>(lds, s.p, n, sc, gl, la, true, ct);
-            s.p += n;
-            d.p += n;
-            s.rem -= n;
-            d.rem -= n;
-            left -= n;
-            sl += n;
-            if (!left) break;
-            if (!c.rem) {  // the chosen side's segment is complete (an empty one: 0, nothing to fold)
-                if (gl == 0) args.seg_out[c.i] = sc;
-                if (sl) acc = fold.apply(acc, sc, sl, gl, pt);
-                sc = 0;
-                sl = 0;
-            }
-            if (!s.rem) s.next();
-            if (!d.rem) d.next();
-        }
+        iov_walk_pieces(
+            s, d, left,
+            [&](uint64_t n) PCRC_WALK_INLINE {
+                sc = u.copy(s, d, left, n, sc);
+                sl += n;
+            },
+            [&]() PCRC_WALK_INLINE {
+                if (!c.rem) {  // the chosen side's segment is complete (an empty one: 0, nothing to fold)
+                    if (gl == 0) args.seg_out[c.i] = sc;
+                    if (sl) acc = fold.apply(acc, sc, sl, gl, pt);
+                    sc = 0;
+                    sl = 0;
+                }
+            });
         if (c.more()) {
             // The walk ended in segment c.i (or before its first byte): its
             // landed prefix, then 0 = the CRC of no bytes for the rest.
@@ -1528,20 +1460,14 @@ __global__ __launch_bounds__(kBlock) void crc32c_copy_iov_seg_kernel(CopyIovSegA
             if (sl) acc = fold.apply(acc, sc, sl, gl, pt);
             for (uint64_t k = c.i + 1 + gl; k < c.end; k += G) args.seg_out[k] = 0u;
         }
-        if (active && gl == 0) {
-            args.out[m] = acc;
-            if (args.copied) args.copied[m] = (args.size ? args.size[m] : ~0ull) - left;
-        }
-    }
+        iov_walk_finish(args, m, active && gl == 0, acc, left);
+    });
 }
 
 // photon_crc32c_copy_msg_iov_seg2_n / photon_crc64ecma_copy_msg_iov_seg2_n
 // (DESIGN.md §4.13): one CRC per segment of BOTH sides. Two kernels on the
-// stream. The walk kernel is crc32c_copy_iov_kernel's (crc64_copy_iov_kernel's)
-// piece loop with the running CRC -- chained from seed_m through the whole
-// message, never reset -- stored at the entry of every segment a cursor
-// leaves or ends in; seg_unscan_kernel then turns the running values into
-// per-segment CRCs in place (seg_unscan.h), without reading payload.
+// stream: the walk kernel (iov_copy_messages<true>, iov_walk.h; CRC-64: a copy
+// of it, crc64_kernels.h) and seg_unscan_kernel.
 template <typename T>
 struct CopyIovSeg2ArgsT {
     const photon_crc_iovec* src;
@@ -1559,69 +1485,12 @@ struct CopyIovSeg2ArgsT {
 };
 typedef CopyIovSeg2ArgsT<uint32_t> CopyIovSeg2Args;
 
-// No SegFold, no PowTable, no multiply: beside crc32c_copy_iov_kernel's loop
-// only the stores. A zero-length segment makes a zero-length piece as there;
-// its entry receives the unchanged running value. The entries behind the
-// segment in which the walk ended are not touched here.
+// No SegFold, no PowTable, no multiply.
 template <int G, int U>
 __global__ __launch_bounds__(kBlock) void crc32c_copy_iov_seg2_kernel(CopyIovSeg2Args args, LaneConsts kc) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
-    constexpr bool kMsgLead = PCRC_MSG_LEAD != 0;
     load_tables<G>(lds, kc);
-
-    constexpr int GPW = 64 / G;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = wave_id();
-    const uint32_t gl = lane & (G - 1);
-    const uint32_t grp = lane / G;
-    const LaneAddr la = lane_addr(lane);
-
-    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
-    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave; wv * GPW < args.nmsg; wv += nwaves) {
-        const uint64_t m = wv * GPW + grp;
-        const bool active = m < args.nmsg;
-        uint32_t acc = args.seed0;
-        uint64_t left = 0;
-        IovCursor<true> s, d;
-        s.begin(args.src, 0, 0);
-        d.begin(args.dst, 0, 0);
-        if (active) {
-            left = args.size ? args.size[m] : ~0ull;
-            if (args.seeds) acc = args.seeds[m];
-            s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
-            d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
-        }
-        while (left && s.more() && d.more()) {
-            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
-            n = n < left ? n : left;
-            const CopyTo ct = copy_begin<G>(s.p, const_cast<uint8_t*>(d.p), n, gl);
-            acc = buffer_crc<G, U, kMsgLead, true>(lds, s.p, n, acc, gl, la, true, ct);
-            s.p += n;
-            d.p += n;
-            s.rem -= n;
-            d.rem -= n;
-            left -= n;
-            if (!left) break;
-            if (!s.rem) {  // the running CRC at the end of source segment s.i
-                if (gl == 0) args.src_seg[s.i] = acc;
-                s.next();
-            }
-            if (!d.rem) {
-                if (gl == 0) args.dst_seg[d.i] = acc;
-                d.next();
-            }
-        }
-        // (an inactive group's cursors are empty)
-        if (gl == 0) {
-            // The segment each side's walk ended in (or before its first byte).
-            if (s.more()) args.src_seg[s.i] = acc;
-            if (d.more()) args.dst_seg[d.i] = acc;
-        }
-        if (active && gl == 0) {
-            args.out[m] = acc;
-            if (args.copied) args.copied[m] = (args.size ? args.size[m] : ~0ull) - left;
-        }
-    }
+    iov_copy_messages<true>(args, Unit32<G, U>(lds));
 }
 
 // The un-scan of the walk's running values (seg_unscan.h), one WAVEFRONT per
@@ -1742,10 +1611,10 @@ typedef CopyIovWindowArgsT<uint32_t> CopyIovWindowArgs;
 // cursor and the cap are held only where they are used (in one loop with two
 // counters every CRC-64 build spilled):
 //   in front of the window   n = min(s.rem, bytes to a)     CopyTo{}: no store
-//   inside it                n = min(s.rem, d.rem, left)    copy_begin, as crc32c_copy_iov_kernel
-//   behind it                n = s.rem                      CopyTo{}: no store
+//   inside it                n = min(s.rem, d.rem, left)    the unit's copy (iov_walk.h)
+//   behind it                n = s.rem                     CopyTo{}: no store
 // The first run ends at a = min(skip, L); the running value there goes to
-// work[2m]. The second is crc32c_copy_iov_kernel's loop: the window closes
+// work[2m]. The second is iov_walk.h's piece loop: the window closes
 // when the cap is used up, the destination is exhausted or the source ends,
 // and the running value there goes to work[2m + 1]. The third reads what is
 // left of the source. Both words are always stored; window_finish_kernel reads
@@ -1756,41 +1625,28 @@ typedef CopyIovWindowArgsT<uint32_t> CopyIovWindowArgs;
 template <int G, int U>
 __global__ __launch_bounds__(kBlock) void crc32c_copy_iov_window_kernel(CopyIovWindowArgs args, LaneConsts kc) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[lds_bytes_for<G>() / 4];
-    constexpr bool kMsgLead = PCRC_MSG_LEAD != 0;
     load_tables<G>(lds, kc);
+    const Unit32<G, U> u(lds);
+    const uint32_t gl = u.gl;
 
-    constexpr int GPW = 64 / G;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = wave_id();
-    const uint32_t gl = lane & (G - 1);
-    const uint32_t grp = lane / G;
-    const LaneAddr la = lane_addr(lane);
-
-    const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
-    for (uint64_t wv = (uint64_t)blockIdx.x * kWaves + wave; wv * GPW < args.nmsg; wv += nwaves) {
-        const uint64_t m = wv * GPW + grp;
+    iov_walk_messages(u, args.nmsg, [&](uint64_t m) PCRC_WALK_INLINE {
         const bool active = m < args.nmsg;
         uint32_t acc = 0;
         IovCursor<true> s;
         s.begin(args.src, 0, 0);
         if (active) s.begin(args.src, args.src_start[m], args.src_start[m + 1]);
-        auto piece = [&](uint64_t n, CopyTo ct) {  // n bytes at the source cursor
-            acc = buffer_crc<G, U, kMsgLead, true>(lds, s.p, n, acc, gl, la, true, ct);
-            s.p += n;
-            s.rem -= n;
-        };
-        auto seg_end = [&] {  // the running CRC at the end of source segment s.i
-            if (!s.rem) {
-                if (gl == 0) args.src_seg[s.i] = acc;
-                s.next();
-            }
+        auto store_end = [&]() PCRC_WALK_INLINE {  // the running CRC at the end of source segment s.i
+            if (gl == 0) args.src_seg[s.i] = acc;
         };
         auto skim = [&](uint64_t cnt) {  // up to cnt source bytes, none stored
             while (cnt && s.more()) {
                 const uint64_t n = s.rem < cnt ? s.rem : cnt;
                 cnt -= n;
-                piece(n, CopyTo{});
-                seg_end();
+                acc = u.rows(s, n, acc, CopyTo{});
+                if (!s.rem) {
+                    store_end();
+                    s.next();
+                }
             }
         };
         skim(active && args.skip ? args.skip[m] : 0ull);
@@ -1802,21 +1658,10 @@ __global__ __launch_bounds__(kBlock) void crc32c_copy_iov_window_kernel(CopyIovW
             left = args.size ? args.size[m] : ~0ull;
             d.begin(args.dst, args.dst_start[m], args.dst_start[m + 1]);
         }
-        while (left && s.more() && d.more()) {
-            uint64_t n = s.rem < d.rem ? s.rem : d.rem;
-            n = n < left ? n : left;
-            const CopyTo ct = copy_begin<G>(s.p, const_cast<uint8_t*>(d.p), n, gl);
-            piece(n, ct);
-            d.p += n;
-            d.rem -= n;
-            left -= n;
-            if (!left) break;
-            seg_end();
-            if (!d.rem) d.next();
-        }
+        iov_walk_pieces(s, d, left, [&](uint64_t n) PCRC_WALK_INLINE { acc = u.copy(s, d, left, n, acc); }, IovNoHook(), store_end);
         if (active && gl == 0) args.work[2 * m + 1] = acc;  // R(b)
         skim(~0ull);
-    }
+    });
 }
 
 // The finish of the windowed walk (window_finish.h), one WAVEFRONT per message

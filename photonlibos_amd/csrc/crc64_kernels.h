@@ -676,6 +676,14 @@ __global__ __launch_bounds__(kBlock) void crc64_batch_kernel(std::conditional_t<
     crc64_batch_run<G, false, COPY>(args, kc, lds, nullptr);
 }
 
+// The group's first lane's value on every lane of the group (the broadcast of
+// buffer_reg64's result between the pieces of a chain).
+template <int G>
+__device__ __forceinline__ uint64_t group_first64(uint64_t r, uint32_t gl) {
+    const uint64_t v = gl == 0 ? r : 0ull;
+    return ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+}
+
 // photon_crc64ecma_gather_msg_n: one lane group per message
 // walks its segments, lands them back to back at dst[m] (the running
 // destination is carried: no prefix sum) and checksums them from the same
@@ -718,16 +726,15 @@ __global__ __launch_bounds__(kBlock) void crc64_gather_kernel(CopyBatch64Args ar
             if (per_seg) {
                 if (gl == 0) args.seg_out[sg] = ~r;
             } else {
-                const uint64_t v = gl == 0 ? r : 0ull;
-                reg = ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+                reg = group_first64<G>(r, gl);
             }
         }
         if (!per_seg && active && gl == 0) args.out[m] = ~reg;
     }
 }
 
-// photon_crc64ecma_copy_msg_iov_n: crc32c_copy_iov_kernel's
-// two-cursor walk (IovCursor, crc32c_kernels.h) with the CRC-64 copying unit.
+// photon_crc64ecma_copy_msg_iov_n: the two-cursor walk
+// (IovCursor and the rules: iov_walk.h) with the CRC-64 copying unit.
 // The raw register is chained from piece to piece and broadcast within the
 // group between them, as crc64_gather_kernel does between segments.
 struct CopyIov64Args {
@@ -743,13 +750,21 @@ struct CopyIov64Args {
     uint64_t seed0;
 };
 
+// Descriptor prefetch of the CRC-64 walk kernels within the 128-VGPR budget
+// (DESIGN.md §4.5): both sides at 64 lanes, the source side alone at 4 and 8,
+// none at 16 and 32 (a descriptor is then loaded when its segment is reached).
+template <int G>
+constexpr bool kPrefetchSrc64 = G == 64 || G <= 8;
+template <int G>
+constexpr bool kPrefetchDst64 = G == 64;
+
+// The CRC-64 walk kernels keep their own copies of iov_walk.h's set-up and
+// piece loop: written through it, they did not compile to what they were
+// (DESIGN.md "The two-cursor walk, written once" has the figures).
 template <int G>
 __global__ __launch_bounds__(kBlock) void crc64_copy_iov_kernel(CopyIov64Args args, LaneConsts64 kc) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
-    // Descriptor prefetch within the 128-VGPR budget: both
-    // sides at 64 lanes, the source side alone at 4 and 8, none at 16 and 32
-    // (a descriptor is then loaded when its segment is reached).
-    constexpr bool kPrefetchSrc = G == 64 || G <= 8, kPrefetchDst = G == 64;
+    constexpr bool kPrefetchSrc = kPrefetchSrc64<G>, kPrefetchDst = kPrefetchDst64<G>;
     load_tables64<G>(lds, kc);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t gl = lane & (G - 1);
@@ -785,9 +800,7 @@ __global__ __launch_bounds__(kBlock) void crc64_copy_iov_kernel(CopyIov64Args ar
             s.rem -= n;
             d.rem -= n;
             left -= n;
-            const uint64_t r = buffer_reg64<G, true>(lds, sp, n, reg, gl, lane, la, true, ct);
-            const uint64_t v = gl == 0 ? r : 0ull;
-            reg = ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+            reg = group_first64<G>(buffer_reg64<G, true>(lds, sp, n, reg, gl, lane, la, true, ct), gl);
             if (!left) break;
             if (!s.rem) s.next();
             if (!d.rem) d.next();
@@ -825,8 +838,7 @@ struct CopyIovSeg64Args {
 template <int G, bool DST>
 __global__ __launch_bounds__(kBlock) void crc64_copy_iov_seg_kernel(CopyIovSeg64Args args, LaneConsts64 kc) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
-    // Descriptor prefetch as crc64_copy_iov_kernel (the 128-VGPR budget).
-    constexpr bool kPrefetchSrc = G == 64 || G <= 8, kPrefetchDst = G == 64;
+    constexpr bool kPrefetchSrc = kPrefetchSrc64<G>, kPrefetchDst = kPrefetchDst64<G>;
     load_tables64<G>(lds, kc);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t gl = lane & (G - 1);
@@ -859,9 +871,7 @@ __global__ __launch_bounds__(kBlock) void crc64_copy_iov_seg_kernel(CopyIovSeg64
             s.rem -= n;
             d.rem -= n;
             left -= n;
-            const uint64_t r = buffer_reg64<G, true>(lds, sp, n, reg, gl, lane, la, true, ct);
-            const uint64_t v = gl == 0 ? r : 0ull;
-            reg = ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+            reg = group_first64<G>(buffer_reg64<G, true>(lds, sp, n, reg, gl, lane, la, true, ct), gl);
             if (!left) break;
             if (!(DST ? d.rem : s.rem)) {  // the chosen side's segment is complete
                 if (gl == 0) args.seg_out[DST ? d.i : s.i] = ~reg;
@@ -883,14 +893,13 @@ __global__ __launch_bounds__(kBlock) void crc64_copy_iov_seg_kernel(CopyIovSeg64
 // photon_crc64ecma_copy_msg_iov_seg2_n: crc64_copy_iov_kernel's
 // walk with the running CRC (~reg, chained from seed_m, never reset) stored at
 // the entry of every segment a cursor leaves or ends in, on both sides, as
-// crc32c_copy_iov_seg2_kernel does; seg_unscan_kernel<Gf64> follows.
+// iov_walk.h's seg2 form does; seg_unscan_kernel<Gf64> follows.
 typedef CopyIovSeg2ArgsT<uint64_t> CopyIovSeg264Args;
 
 template <int G>
 __global__ __launch_bounds__(kBlock) void crc64_copy_iov_seg2_kernel(CopyIovSeg264Args args, LaneConsts64 kc) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[k64FLdsBytes / 4];
-    // Descriptor prefetch as crc64_copy_iov_kernel (the 128-VGPR budget).
-    constexpr bool kPrefetchSrc = G == 64 || G <= 8, kPrefetchDst = G == 64;
+    constexpr bool kPrefetchSrc = kPrefetchSrc64<G>, kPrefetchDst = kPrefetchDst64<G>;
     load_tables64<G>(lds, kc);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t gl = lane & (G - 1);
@@ -924,9 +933,7 @@ __global__ __launch_bounds__(kBlock) void crc64_copy_iov_seg2_kernel(CopyIovSeg2
             s.rem -= n;
             d.rem -= n;
             left -= n;
-            const uint64_t r = buffer_reg64<G, true>(lds, sp, n, reg, gl, lane, la, true, ct);
-            const uint64_t v = gl == 0 ? r : 0ull;
-            reg = ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+            reg = group_first64<G>(buffer_reg64<G, true>(lds, sp, n, reg, gl, lane, la, true, ct), gl);
             if (!left) break;
             if (!s.rem) {  // the running CRC at the end of source segment s.i
                 if (gl == 0) args.src_seg[s.i] = ~reg;
@@ -991,9 +998,7 @@ __global__ __launch_bounds__(kBlock) void crc64_copy_iov_window_kernel(CopyIovWi
             const uint8_t* sp = s.p;
             s.p += n;
             s.rem -= n;
-            const uint64_t r = buffer_reg64<G, true, 3>(lds, sp, n, reg, gl, lane, la, true, ct);
-            const uint64_t v = gl == 0 ? r : 0ull;
-            reg = ((uint64_t)group_xor<G>((uint32_t)(v >> 32)) << 32) | group_xor<G>((uint32_t)v);
+            reg = group_first64<G>(buffer_reg64<G, true, 3>(lds, sp, n, reg, gl, lane, la, true, ct), gl);
         };
         auto seg_end = [&] {  // the running CRC at the end of source segment s.i
             if (!s.rem) {
